@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched Optimax Rogue tick engine on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it sets up,
+warms up, times the K steps, writes the last step's outputs with
+`--dump-outputs DIR`, and prints the result line.  `--full` adds every other
+measurement (the extras, the CPU baseline and, with N > 1 ranks, the C5
+block) to the same line.
 
 `--gpus N` outside torchrun starts the N rank processes itself (one per GPU,
 torch.distributed.run on 127.0.0.1, before this process touches the GPU) and
@@ -26,9 +32,17 @@ trajectory buffer -- nothing is skipped.  The launches are issued through a
 pre-bound launcher (one ctypes call each) with HIP events created beforehand,
 so the timed region is the kernels back to back.
 
-Extras (rank 0, 1 GPU): the unfused path (orx_policy + orx_step per tick,
-captured in a HIP graph) at the config batch, the per-tick kernels at 2^21
-games, C2 and C5.
+`--dump-outputs DIR` writes what the last timed step returned to its caller
+as DIR/<name>.npy (float64): `obs` [ticks, 14, n] and `act` [ticks, n, 2], the
+trajectory rows of a fixed, seeded sample of n games (`game_ids` names them,
+by global id; the whole buffers are ~0.5 GB), `obs_sum` [ticks, 14], every
+row summed over all games (exact in int64), and `episode_returns` [2, games],
+the per-game (return sum, episode count) the line's episode figures come
+from.  The workload is seeded, so the same arguments give the same files.
+
+Extras (`--full`, rank 0, 1 GPU): the unfused path (orx_policy + orx_step
+per tick, captured in a HIP graph) at the config batch, the per-tick kernels
+at 2^21 games, C2 and C5.
 
 Rank 0 prints one JSON line.
 """
@@ -291,6 +305,43 @@ def timed_launches(torch, launch, n):
         evs.append((a, b))
     torch.cuda.synchronize()
     return [a.elapsed_time(b) * 1e-3 for a, b in evs]
+
+
+DUMP_SEED = 20240607     # the sample of games --dump-outputs writes
+DUMP_GAMES = 2048        # at most this many games' trajectory rows ...
+DUMP_BYTES = 48 << 20    # ... and this many bytes of them, over all ranks
+
+
+def dump_outputs(torch, out_dir, obs, act, returns, offset, rank, world):
+    """--dump-outputs: the last timed step's outputs as float64 .npy files
+    (module docstring).  `obs` / `act`: this rank's per-shard trajectory
+    buffers (shards contiguous by game id from `offset`); `returns`: the
+    gathered [2, games] episode returns (written by rank 0).  With more than
+    one rank each rank writes its own shard's files as <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    T, rows = obs[0].shape[0], obs[0].shape[1]
+    B = sum(o.shape[2] for o in obs)
+    n = max(1, min(B, DUMP_GAMES // world, DUMP_BYTES // world // (T * (rows + 2) * 8)))
+    local = np.sort(np.random.RandomState(DUMP_SEED).choice(B, n, replace=False))
+    o_parts, a_parts, start = [], [], 0
+    o_sum = torch.zeros((T, rows), dtype=torch.int64, device=obs[0].device)
+    for o, a in zip(obs, act):
+        cnt = o.shape[2]
+        sel = local[(local >= start) & (local < start + cnt)] - start
+        idx = torch.as_tensor(sel, dtype=torch.int64, device=o.device)
+        o_parts.append(o.index_select(2, idx).cpu().numpy())
+        a_parts.append(a.index_select(1, idx).cpu().numpy())
+        o_sum += o.sum(dim=2, dtype=torch.int64)
+        start += cnt
+    tag = f"_rank{rank}" if world > 1 else ""
+    out = {"obs": np.concatenate(o_parts, axis=2), "act": np.concatenate(a_parts, axis=1),
+           "game_ids": offset + local, "obs_sum": o_sum.cpu().numpy()}
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), np.asarray(arr, dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(out_dir, "episode_returns.npy"),
+                returns.cpu().numpy().astype(np.float64))
 
 
 def extras(torch, cfg, dev, B_cfg, K, large_rollout=False):
@@ -751,8 +802,8 @@ def launch_check(args) -> None:
         dist.all_gather_object(ranks, mine)
     if rank == 0:
         line = {"n_gpus": world, "global_batch": G, "ranks": ranks}
-        if world > 1 and not args.no_c5:
-            # the configs[4] block the N > 1 line carries (c5_sharded)
+        if args.full and world > 1 and not args.no_c5:
+            # the configs[4] block the N > 1 --full line carries (c5_sharded)
             line["c5"] = {"global_batch": C5_GLOBAL,
                           "ranks": [{"rank": x["rank"], **x.pop("c5")} for x in ranks]}
         for x in ranks:
@@ -780,9 +831,18 @@ def main():
                          "consumes)")
     ap.add_argument("--streams", type=int, default=2,
                     help="shards of the GPU's batch on concurrent HIP streams")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64; a "
+                         "seeded sample of games' trajectory rows, every row's sum over all "
+                         "games, the per-game episode returns)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the extras (other "
+                         "kernels, shapes and configs), the CPU baseline and, with N > 1 ranks, "
+                         "the C5 block; off by default")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full, skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, skip the extras")
     ap.add_argument("--large", action="store_true",
                     help="extras also time the headline rollout kernel at 2^21 games")
     ap.add_argument("--dist-backend", default="nccl",
@@ -790,8 +850,8 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="every rank uses cuda:0 (rehearsing N ranks on a 1-GPU box)")
     ap.add_argument("--no-c5", action="store_true",
-                    help="with N > 1 ranks, skip the configs[4] block (C5: 131,072 StaircaseBot "
-                         "games strong-sharded over the ranks, c5_sharded)")
+                    help="with --full and N > 1 ranks, skip the configs[4] block (C5: 131,072 "
+                         "StaircaseBot games strong-sharded over the ranks, c5_sharded)")
     ap.add_argument("--c5-steps", type=int, default=20,
                     help="timed steps of each C5 block (N > 1 ranks)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
@@ -895,10 +955,12 @@ def main():
     mean_ret = float(allrets[0].sum().item()) / max(1, episodes)
 
     value = G * chunk * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, obs, act, allrets, offset, rank, world)
     # BASELINE.json configs[4] on the same ranks: C5's 131,072 games
     # strong-sharded over them (every rank takes part: barriers, collectives)
     c5 = None
-    if world > 1 and not args.no_c5:
+    if args.full and world > 1 and not args.no_c5:
         del obs, act, launch, eng
         torch.cuda.empty_cache()
         c5 = c5_sharded(torch, dist, dev, rank, world, coll_dev, args.c5_steps)
@@ -911,12 +973,12 @@ def main():
                     and tr.get("build_id") == _lib.build_id():
                 traffic = tr.get("hbm_bytes_per_step")
         extra = None
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             del obs, act, launch, eng
             torch.cuda.empty_cache()
             extra = extras(torch, cfg, dev, B, cfg.n_npcs, args.large)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(cfg.to_dict(), args.cpu_seconds)
         if args.strong:
             metric = (f"env-steps/sec (whole node) at global batch={G}, 64x64 grid; "
@@ -987,7 +1049,7 @@ def main():
             "ranks": ranks,
             "extras": extra,
         }
-        if world > 1:
+        if world > 1 and args.full:
             result["c5"] = c5
         print(json.dumps(result), flush=True)
     if world > 1:

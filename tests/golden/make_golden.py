@@ -981,11 +981,58 @@ def philox_kat():
     ]
 
 
+def make_bot_moves(R):
+    """kat_bot_moves.npz: the reference's StaircaseBot / RandomBot classes
+    run on the compat views of tests/test_compat.py's walks (which assert the
+    moves against the oracle's policies as they go); every call's move and,
+    for the StaircaseBots, what the view showed the bot (test_compat.bot_saw)
+    are stored for the tests' RecordedBot."""
+    for p in (os.path.dirname(os.path.dirname(HERE)), os.path.dirname(HERE)):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import test_compat as tc
+    from oracle import oracle
+    oracle.build()
+
+    class Recorder:
+        def __init__(self, bot, iden, staircase=True):
+            self.bot, self.iden, self.staircase, self.moves, self.seen = bot, iden, staircase, [], []
+
+        def move(self, view):
+            m = int(self.bot.move(view))
+            self.moves.append(m)
+            if self.staircase:
+                self.seen.append(tc.bot_saw(view, self.iden))
+            return m
+
+    out = {}
+    for case, walk in (("stairs", tc.staircasebot_walk), ("bank", tc.staircasebot_bank_walk)):
+        recs = {}
+
+        def make_bot(p, i):
+            recs[p, i] = Recorder(R.staircasebot.StaircaseBot(1 + p), 1 + p)
+            return recs[p, i]
+        walk(oracle, make_bot)
+        B = 1 + max(i for _, i in recs)
+        # [T, B, 2] moves and [T, B, 2, 5] views, player last as in the action arrays
+        out[case + "_moves"] = np.stack([np.stack([recs[p, i].moves for p in range(2)], -1)
+                                         for i in range(B)], 1).astype(np.int8)
+        out[case + "_seen"] = np.stack([np.stack([recs[p, i].seen for p in range(2)], 1)
+                                        for i in range(B)], 1).astype(np.int16)
+    R.randombot.random = random.Random(0)   # the module's own RNG, as in the stock bot runner
+    rec = Recorder(R.randombot.RandomBot(1), 1, staircase=False)
+    tc.randombot_walk(oracle, rec)
+    out["random_moves"] = np.array(rec.moves, np.int8)
+    np.savez_compressed(os.path.join(HERE, "kat_bot_moves.npz"), **out)
+
+
 def main():
     for ctr, key, want in philox_kat():
         assert philox4x32_10(ctr, key) == want
     R = import_reference()
     only = sys.argv[1:]
+    if not only or "bot_moves" in only:
+        make_bot_moves(R)
     if not only or "kat" in only:
         make_scenarios(R)
     for name, spec in CASES.items():

@@ -1,9 +1,11 @@
 """CPU: the reference-schema views (compat.game_state) drive the reference's
 own bots unchanged.  The snapshots come from the oracle; the bots are the
-reference's RandomBot / StaircaseBot classes when /root/reference is present
-in this (build) container, otherwise the test is skipped."""
+reference's RandomBot / StaircaseBot classes as recorded in
+tests/golden/kat_bot_moves.npz: tests/golden/make_golden.py ran the walks
+below with the reference's classes on these views and stored, for every call,
+what the bot read from its view and the move it returned; RecordedBot checks
+that the view shows the same and returns that move."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -11,16 +13,40 @@ import pytest
 from optimax_rogue_amd import EnvConfig, Move
 from optimax_rogue_amd.compat import game_state
 
-REF = "/root/reference"
+BOT_MOVES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                         "kat_bot_moves.npz")
 
 
-def _ref_bots():
-    if not os.path.isdir(REF):
-        pytest.skip("reference not present (GPU box)")
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_golden  # installs the inflection stub + import path only
-    R = make_golden.import_reference()
-    return R
+def bot_saw(view, iden):
+    """What a StaircaseBot reads from its view: its own entity's depth and
+    cell, and that depth's staircase."""
+    me = view.iden_lookup[iden]
+    sx, sy = view.world.dungeons[me.depth].staircase()
+    return (int(me.depth), int(me.x), int(me.y), int(sx), int(sy))
+
+
+class RecordedBot:
+    """One reference bot's recorded calls: ``moves[k]`` is what the
+    reference's class returned on its k-th call, ``seen[k]`` (StaircaseBot
+    only) what its view showed it then (bot_saw)."""
+
+    def __init__(self, iden, moves, seen=None):
+        self.iden, self.moves, self.seen, self.k = iden, moves, seen, 0
+
+    def move(self, view):
+        k, self.k = self.k, self.k + 1
+        if self.seen is not None:
+            assert bot_saw(view, self.iden) == tuple(int(v) for v in self.seen[k]), k
+        return int(self.moves[k])
+
+
+def _recorded(case):
+    """make_bot(p, i) for the StaircaseBot walks below: game i's player p + 1
+    bot of ``case`` replayed from the fixture (moves [T, B, 2], seen
+    [T, B, 2, 5])."""
+    z = np.load(BOT_MOVES)
+    moves, seen = z[case + "_moves"], z[case + "_seen"]
+    return lambda p, i: RecordedBot(1 + p, moves[:, i, p], seen[:, i, p])
 
 
 def test_views_schema(oracle_lib):
@@ -49,13 +75,15 @@ def test_views_schema(oracle_lib):
             assert world[depth] == dv.staircase()
 
 
-def test_reference_staircasebot_on_views(oracle_lib):
-    R = _ref_bots()
+def staircasebot_walk(oracle_lib, make_bot):
+    """60 ticks of 32 games: each tick every bot (``make_bot(p, i)``: player
+    p + 1 of game i) moves on its view, the moves equal the oracle's
+    StaircaseBot policy."""
     cfg = EnvConfig(width=10, height=7, max_ticks=80)
     B = 32
     o = oracle_lib.Oracle(cfg.to_dict(), B, 9)
     o.reset()
-    bots = [[R.staircasebot.StaircaseBot(1 + p) for _ in range(B)] for p in range(2)]
+    bots = [[make_bot(p, i) for i in range(B)] for p in range(2)]
     for t in range(60):
         snap = o.export()
         want = o.policy(2, 2)
@@ -68,18 +96,24 @@ def test_reference_staircasebot_on_views(oracle_lib):
         o.step(want)
 
 
-def test_reference_randombot_on_views(oracle_lib):
-    R = _ref_bots()
+def test_reference_staircasebot_on_views(oracle_lib):
+    staircasebot_walk(oracle_lib, _recorded("stairs"))
+
+
+def randombot_walk(oracle_lib, bot):
+    """One RandomBot (player 1) asked once on each of 4 games' views."""
     cfg = EnvConfig(width=8, height=8)
     o = oracle_lib.Oracle(cfg.to_dict(), 4, 1)
     o.reset()
     snap = o.export()
-    bot = R.randombot.RandomBot(1)
-    import random as _r
-    R.randombot.random = _r.Random(0)   # the module's own RNG, as in the stock bot runner
     for i in range(4):
         gs = game_state(snap, i, cfg)
         assert Move(int(bot.move(gs.view_for(gs.iden_lookup[1])))) in list(Move)
+
+
+def test_reference_randombot_on_views(oracle_lib):
+    # (recorded with the module's own RNG, random.Random(0), as in the stock bot runner)
+    randombot_walk(oracle_lib, RecordedBot(1, np.load(BOT_MOVES)["random_moves"]))
 
 
 def oracle_view(o, g, cfg):
@@ -159,7 +193,10 @@ def test_dungeon_bank_tables():
 def test_reference_staircasebot_on_bank_views(oracle_lib):
     """The reference's StaircaseBot on views of an explicit-grid game walks
     to the bank layout's first staircase, as the oracle's policy does."""
-    R = _ref_bots()
+    staircasebot_bank_walk(oracle_lib, _recorded("bank"))
+
+
+def staircasebot_bank_walk(oracle_lib, make_bot):
     from golden_util import Fixture
     fx = Fixture("bank_single_separated")
     from optimax_rogue_amd import DungeonBank
@@ -168,7 +205,7 @@ def test_reference_staircasebot_on_bank_views(oracle_lib):
     B = fx.G
     o = oracle_lib.Oracle(fx.cfg, B, fx.seed, 0, layouts=fx.layouts)
     o.reset()
-    bots = [[R.staircasebot.StaircaseBot(1 + p) for _ in range(B)] for p in range(2)]
+    bots = [[make_bot(p, i) for i in range(B)] for p in range(2)]
     for t in range(40):
         snap = o.export()
         want = o.policy(2, 2)

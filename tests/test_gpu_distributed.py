@@ -92,15 +92,15 @@ def test_bench_gpus_2_runs_two_ranks():
     itself: here both on cuda:0 with the gloo gather (--same-device; RCCL takes
     one rank per device), as the driver's SCALE run does with one GPU each.
     The line reports n_gpus 2, both ranks' shards and the returns gather,
-    and the configs[4] (C5) block timed on the same ranks."""
+    and, with `--full`, the configs[4] (C5) block timed on the same ranks."""
     root = os.path.dirname(HERE)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--same-device", "--dist-backend", "gloo", "--batch", "8192",
-                        "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
-                        "--c5-steps", "2"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-extras",
+                        "--no-cpu-baseline", "--c5-steps", "2"],
                        env=env, capture_output=True, text=True, timeout=110, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

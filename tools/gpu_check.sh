@@ -16,7 +16,7 @@ if [ "${2:-tests}" = tests ]; then
     --timeout-method thread > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
   tail -3 $O/pytest.log
 fi
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 cut -c1-400 $O/bench.json
 if [ "${3:-}" = rehearse ]; then
   for MODE in weak strong; do

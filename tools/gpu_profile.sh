@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5"
+BENCH="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full"
 if [ "${2:-tests}" = tests ]; then
   timeout -k 10 600 python3 -u -m pytest $R/tests -m gpu -x -q --timeout 120 \
     --timeout-method thread > $O/pytest.log 2>&1
@@ -18,7 +18,7 @@ fi
 timeout -k 10 300 $BENCH > $O/bench.json 2> $O/bench.err
 cat $O/bench.json | cut -c1-400
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv \
-  -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_under_trace.json 2> $O/trace.err
+  -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_under_trace.json 2> $O/trace.err
 f=$(find $O/trace -name "run_kernel_trace.csv" | head -1)
 python3 $R/tools/ktrace_summary.py $f > $O/kernel_trace_summary.txt
 KNAME=$(python3 -c "import json,sys; print(json.load(open(sys.argv[1]))['roofline']['kernel'])" $O/bench.json)

@@ -11,7 +11,7 @@ mkdir -p $O
 cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 fatal() { case $1 in 124|134|137|139) echo "step $2 ended with $1: stopping"; exit $1;; esac; }
-timeout -k 10 420 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout -k 10 420 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 rc=$?; echo "bench rc=$rc"; cut -c1-300 $O/bench.json; fatal $rc bench
 if [ $# -gt 0 ]; then
   bash tools/gpu_ab_small.sh $TAG "$@"
