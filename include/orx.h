@@ -358,9 +358,10 @@ typedef struct orx_state {
 int orx_abi_version(void);
 
 /* Source hash the library was built from: the first 16 hex digits of the
- * SHA-256 of orx_engine.hip followed by include/orx.h (build.py), so a test
- * can prove the loaded library is the tree's own kernel ("unknown" for a
- * build made outside build.py).  No reference counterpart. */
+ * SHA-256 of orx_engine.hip followed by include/orx.h, orx_view.hip and
+ * include/orx_view.h (build.py), so a test can prove the loaded library is
+ * the tree's own kernels ("unknown" for a build made outside build.py).  No
+ * reference counterpart. */
 const char* orx_build_id(void);
 
 /* Games per wave orx_rollout launches for a batch of n_games (1..64, a power

@@ -11,7 +11,7 @@ from .enums import (CombatFlag, DungeonDespawningStrategy, Move, NpcPolicy, OBS_
 
 __all__ = ["EnvConfig", "DungeonBank", "Move", "UpdateResult", "DungeonDespawningStrategy", "Tile", "CombatFlag",
            "StartMode", "Policy", "NpcPolicy", "OBS_FIELDS", "BatchedEngine", "StreamShardedEngine", "BatchedUpdater",
-           "VecEnv"]
+           "VecEnv", "render_view"]
 
 
 def __getattr__(name):
@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == "VecEnv":
         from .vecenv import VecEnv
         return VecEnv
+    if name == "render_view":
+        from .view import render_view
+        return render_view
     raise AttributeError(name)

@@ -58,6 +58,9 @@ EXPORTS = ("orx_abi_version", "orx_last_error", "orx_validate_cfg", "orx_reset",
            "orx_rollout_shape", "orx_rollout_concurrent", "orx_env_step",
            "orx_rollout_ex", "orx_env_step_ex", "orx_step_n", "orx_max_events",
            "orx_step_n_ex", "orx_env_step_args")
+# the entry points of include/orx_view.h (a header of its own: EXPORTS is
+# exactly what orx.h declares)
+VIEW_EXPORTS = ("orx_view",)
 
 
 def load() -> ctypes.CDLL:
@@ -136,6 +139,10 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "orx_dstore_depths"):
         L.orx_dstore_depths.restype = ctypes.c_int
         L.orx_dstore_depths.argtypes = [P(OrxCfg)]
+    # include/orx_view.h
+    if hasattr(L, "orx_view"):
+        L.orx_view.restype = ctypes.c_int
+        L.orx_view.argtypes = [P(OrxCfg), P(OrxState), i32, i32, vp, vp, i64, vp]
     v = L.orx_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liborx.so ABI {v} != expected {ABI_VERSION}")

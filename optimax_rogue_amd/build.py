@@ -27,6 +27,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 SRC = os.path.join(PKG_DIR, "csrc", "orx_engine.hip")
 HDR = os.path.join(ROOT, "include", "orx.h")
+# the egocentric map view (orx_view): one more object of the library
+VIEW_SRC = os.path.join(PKG_DIR, "csrc", "orx_view.hip")
+VIEW_HDR = os.path.join(ROOT, "include", "orx_view.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -73,11 +76,12 @@ def built_id(path: str = OUT):
 
 def source_id(defines: Iterable[str] = ()) -> str:
     """The id orx_build_id() of a library built from these sources returns:
-    the first 16 hex digits of SHA-256(orx_engine.hip || orx.h), and for a
+    the first 16 hex digits of SHA-256(orx_engine.hip || orx.h || orx_view.hip
+    || orx_view.h), and for a
     build with extra definitions ``+`` and their sorted list (so the product
     id is exactly the sources' hash and no diagnostic build shares it)."""
     h = hashlib.sha256()
-    for p in (SRC, HDR):
+    for p in (SRC, HDR, VIEW_SRC, VIEW_HDR):
         with open(p, "rb") as f:
             h.update(f.read())
     d = sorted(defines)
@@ -108,7 +112,7 @@ def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
     if any(d.split("=")[0] == "ORX_STAMPS" for d in defines):
         # one translation unit (the stamps buffer is a device global read back
         # by the host side, so every kernel must live in the host's unit)
-        cmd = base + ["-shared", "-o", out + ".tmp", SRC]
+        cmd = base + ["-shared", "-o", out + ".tmp", SRC, VIEW_SRC]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -122,7 +126,7 @@ def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
 # the host side, every kernel instance declared extern; parts 1..NPARTS-1:
 # their share of the explicit instantiations, orx_engine.hip "Kernel
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
-# translation unit.
+# translation unit.  orx_view.hip (small) is one more object, compiled first.
 NPARTS = 16
 
 
@@ -133,10 +137,12 @@ def _build_parts(base, out, verbose=False, jobs=None):
         objs = [os.path.join(tmp, f"part{k}.o") for k in range(NPARTS)]
         cmds = [base + ["-c", f"-DORX_NPARTS={NPARTS}", f"-DORX_PART={k}", "-o", objs[k], SRC]
                 for k in range(NPARTS)]
+        objs.append(os.path.join(tmp, "view.o"))
+        cmds.append(base + ["-c", "-o", objs[-1], VIEW_SRC])
         if verbose:
             print(" ".join(cmds[0]) + f"  (parts 0..{NPARTS - 1}, {jobs} at a time)")
         # the heaviest parts first (the paired and one-lane rollouts)
-        order = list(range(1, NPARTS)) + [0]
+        order = list(range(1, NPARTS)) + [0, NPARTS]
         running, failed = [], []
         while order or running:
             while order and len(running) < jobs:

@@ -442,6 +442,46 @@ class BatchedEngine:
                    int(obs_format), self.B, self.seed, self.game_offset, int(self.concurrency),
                    self._stream())
 
+    def view(self, radius: int, player: int = 0, health: bool = False, out=None):
+        """orx_view (include/orx_view.h): the egocentric map window of
+        ``player`` (0 / 1) of every game, uint8 [n_games, V, V] with V = 2 *
+        radius + 1 (1 <= radius <= 15), written by one launch on the current
+        stream from the resident state (no host sync, no state change; it can
+        be captured in a graph behind a step).  ``cells[b, j, i]`` is grid cell
+        (px + i - radius, py + j - radius): tile bits, VIEW_PLAYER, VIEW_NPC
+        and the item bits (optimax_rogue_amd.view; ``view.decode`` gives
+        planes).  With ``health`` returns ``(cells, health)``, the second
+        plane the flagged occupant's health.  ``out`` (a tensor, or a pair
+        with ``health``) is written and returned instead of fresh tensors.
+        The host reference is ``view.render_view(self.snapshot(), ...)``."""
+        from .view import check_view_args
+        check_view_args(player, radius)
+        if not hasattr(self.lib, "orx_view"):
+            raise RuntimeError("liborx.so has no orx_view -- rebuild it "
+                               "(python -m optimax_rogue_amd.build)")
+        V = 2 * int(radius) + 1
+        shape = (self.B, V, V)
+        if out is None:
+            outs = [torch.empty(shape, dtype=torch.uint8, device=self.device)
+                    for _ in range(2 if health else 1)]
+        else:
+            outs = list(out) if isinstance(out, (tuple, list)) else [out]
+            if len(outs) != (2 if health else 1):
+                raise ValueError("out must be one tensor, or (cells, health) with health=True")
+            # the kernel writes [n_games, V, V] blindly: a wrong buffer would
+            # be an out-of-bounds device access, so it is refused here
+            for t in outs:
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 \
+                        or tuple(t.shape) != shape or not t.is_contiguous() \
+                        or t.device != self.device:
+                    raise ValueError(f"out must be a contiguous uint8 {shape} tensor on "
+                                     f"{self.device}")
+            if health and outs[0].data_ptr() == outs[1].data_ptr():
+                raise ValueError("out: cells and health must be different tensors")
+        self._call("orx_view", int(player), int(radius), _ptr(outs[0]),
+                   _ptr(outs[1]) if health else None, self.B, self._stream())
+        return (outs[0], outs[1]) if health else outs[0]
+
     def _check_actions(self, a: torch.Tensor, what: str) -> None:
         # the kernels index [n_games, 2] blindly: a wrong buffer would be an
         # out-of-bounds device access, so it is refused here

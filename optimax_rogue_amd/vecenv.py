@@ -122,6 +122,14 @@ class VecEnv:
                             e.p_x[1], e.p_y[1], e.p_depth[1], e.p_health[1],
                             e.tick, e.status, e.st_x[0], e.st_y[0], e.st_x[1], e.st_y[1]], dim=1)
 
+    def view(self, radius: int, player: int = 0, health: bool = False, out=None):
+        """The egocentric map window around ``player`` (0: the learner) of every
+        game -- the NPCs, walls, staircases and items in sight that the
+        14-field row does not carry: uint8 [n_games, 2 * radius + 1, 2 *
+        radius + 1] cell codes (``BatchedEngine.view``; one launch, no host
+        sync).  Call it after ``step`` (or ``reset``) for that state's view."""
+        return self.engine.view(radius, player=player, health=health, out=out)
+
     @staticmethod
     def outcome(before: torch.Tensor, after: torch.Tensor):
         """(reward, done) of a transition between two status tensors.  A game
