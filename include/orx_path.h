@@ -1,0 +1,96 @@
+/*
+ * orx_path.h -- the staircase distance field of liborx.so: how far every tile
+ * of a dungeon is from the nearest StaircaseDown along walkable cells, and
+ * the move that gets a player one step closer.
+ *
+ * The reference's one non-random scripted player, StaircaseBot ("rushes as
+ * quickly as possible to the staircase", optimax_rogue_bots/staircasebot.py:
+ * 1-21), steps along the larger delta; the updater turns a step into a Wall
+ * into Stay (optimax_rogue/logic/updater.py:89-98), so on a map with interior
+ * walls it stops at the first one in its way.  The distance a walking entity
+ * actually has to cover is a breadth-first search over is_blocked
+ * (world.py:41-46) with calculate_pos's four moves (updater.py:340-351).
+ * orx_path_field computes it for every layout of a dungeon bank;
+ * orx_path_query reads it for one player of every game.  Nothing in the tick
+ * changes: this is a definition over the tiles, not a game rule.
+ *
+ * It is a header of its own so that orx.h's list of entry points stays what
+ * it is; the conventions (caller-owned device pointers, asynchronous on the
+ * caller's stream, ORX_OK or a negative code with orx_last_error) are orx.h's.
+ * ORX_ABI_VERSION is unchanged: no existing struct or entry point changes.
+ */
+#ifndef ORX_PATH_H
+#define ORX_PATH_H
+
+#include "orx.h"
+#include "orx_view.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- one cell of the field (uint16) --------------------------------------
+ * 0 on a StaircaseDown tile, else the number of moves of the shortest
+ * 4-connected path over in-grid tiles that are not Wall to the nearest
+ * StaircaseDown (any of them descends, updater.py:205-206), or: */
+#define ORX_PATH_WALL        0xFFFF   /* a Wall tile, or a cell outside the W x H grid */
+#define ORX_PATH_UNREACHABLE 0xFFFE   /* not Wall, but no walkable path to any staircase */
+/* A finite value never reaches the sentinels: a path of 0xFFFE moves needs
+ * that many non-Wall tiles in a row, and a bank has at most 65,536 tiles. */
+
+/* The field of every layout of a bank: cfg->n_layouts = L in 1..32767 layouts
+ * of cfg->width x cfg->height tiles (W, H >= 1, W * H <= 65536: every bank
+ * DungeonBank accepts; of cfg only these three fields are read).  bank_tiles
+ * is uint8 [L][W * H], flat index x * H + y, as in orx_state_t; field is
+ * uint16 [L][W * H] in the same layout.  The result is the unique fixed point
+ * of d = min(d, 1 + min over the open neighbours) from d = 0 on the
+ * staircases, so it does not depend on the order of the relaxation.  One
+ * launch, no host sync; a layout's plane lives in LDS (2 * (W * H + min(W, H)
+ * + 1) bytes, 128.5 KiB at the limit).  ORX_EINVAL: a NULL pointer or
+ * dimensions outside the above; ORX_EIO: the device refuses that much LDS. */
+int orx_path_field(const orx_cfg_t* cfg, const uint8_t* bank_tiles, uint16_t* field, void* stream);
+
+/* For `player` (0 = player 1, 1 = player 2) of every game, on that player's
+ * depth.  The value of cell (x, y):
+ *   outside the W x H grid: ORX_PATH_WALL;
+ *   a dungeon bank (cfg->n_layouts > 0): field[p_layout[player]][x * H + y]
+ *     (field: what orx_path_field wrote for the state's bank_tiles; the layout
+ *     index is clamped to the bank as orx_view clamps it);
+ *   EmptyDungeonGenerator (n_layouts == 0; field is NULL and ignored):
+ *     ORX_PATH_WALL on the border, else |x - st_x[player]| + |y - st_y[player]|
+ *     -- exact, because the interior has no walls.
+ * Outputs (each may be NULL, not all three):
+ *   dist   int32 [n_games]: the value of the player's own cell; -1 where it is
+ *          ORX_PATH_UNREACHABLE.
+ *   move   int8 [n_games]: the first of ORX_MOVE_UP (y - 1), RIGHT (x + 1),
+ *          DOWN (y + 1), LEFT (x - 1), in that order, whose target cell has
+ *          the value own - 1; ORX_MOVE_STAY when the own value is 0 or a
+ *          sentinel.  Entities are not part of the field: a move onto a cell
+ *          holding an NPC or the other player is an attack, as handle_move
+ *          resolves it.
+ *   window uint16 [n_games][V][V], V = 2 * radius + 1, 1 <= radius <=
+ *          ORX_VIEW_MAX_RADIUS: the values in orx_view's geometry,
+ *          window[(b * V + j) * V + i] = cell (px + i - radius, py + j -
+ *          radius).  When window is NULL, radius is ignored.
+ * Reads the state, writes only its outputs; no host sync (it can be captured
+ * in a graph behind orx_env_step), no random words; nothing depends on
+ * status.  ORX_EINVAL: player not 0 / 1, a bad radius with a window, three
+ * NULL outputs, n_games <= 0, a configuration orx_validate_cfg refuses, a
+ * bank without field or p_layout, or a NULL state pointer that is read (p_x,
+ * p_y; st_x and st_y without a bank). */
+int orx_path_query(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t* field,
+                   int32_t player, int32_t radius,
+                   int32_t* dist, int8_t* move, uint16_t* window,
+                   int64_t n_games, void* stream);
+
+/* The id of the sources this part of the library was built from: the first 16
+ * hex digits of SHA-256(orx_path.hip || orx_path.h), as orx_build_id() is of
+ * the engine's and the view's files (which therefore keeps its value, and
+ * with it every profile keyed on it, when only the files here change). */
+const char* orx_path_build_id(void);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* ORX_PATH_H */

@@ -61,6 +61,8 @@ EXPORTS = ("orx_abi_version", "orx_last_error", "orx_validate_cfg", "orx_reset",
 # the entry points of include/orx_view.h (a header of its own: EXPORTS is
 # exactly what orx.h declares)
 VIEW_EXPORTS = ("orx_view",)
+# ... and of include/orx_path.h
+PATH_EXPORTS = ("orx_path_field", "orx_path_query", "orx_path_build_id")
 
 
 def load() -> ctypes.CDLL:
@@ -143,6 +145,16 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "orx_view"):
         L.orx_view.restype = ctypes.c_int
         L.orx_view.argtypes = [P(OrxCfg), P(OrxState), i32, i32, vp, vp, i64, vp]
+    # include/orx_path.h
+    if hasattr(L, "orx_path_field"):
+        L.orx_path_field.restype = ctypes.c_int
+        L.orx_path_field.argtypes = [P(OrxCfg), vp, vp, vp]
+    if hasattr(L, "orx_path_query"):
+        L.orx_path_query.restype = ctypes.c_int
+        L.orx_path_query.argtypes = [P(OrxCfg), P(OrxState), vp, i32, i32, vp, vp, vp, i64, vp]
+    if hasattr(L, "orx_path_build_id"):
+        L.orx_path_build_id.restype = ctypes.c_char_p
+        L.orx_path_build_id.argtypes = []
     v = L.orx_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liborx.so ABI {v} != expected {ABI_VERSION}")
@@ -159,3 +171,10 @@ def check(fn: str, code: int) -> None:
 def build_id() -> str:
     """orx_build_id() of the loaded library (build.source_id() of its sources)."""
     return load().orx_build_id().decode()
+
+
+def path_build_id() -> str:
+    """orx_path_build_id() of the loaded library (build.path_id() of its
+    sources; "" for a library built before include/orx_path.h)."""
+    L = load()
+    return L.orx_path_build_id().decode() if hasattr(L, "orx_path_build_id") else ""

@@ -30,6 +30,10 @@ HDR = os.path.join(ROOT, "include", "orx.h")
 # the egocentric map view (orx_view): one more object of the library
 VIEW_SRC = os.path.join(PKG_DIR, "csrc", "orx_view.hip")
 VIEW_HDR = os.path.join(ROOT, "include", "orx_view.h")
+# the staircase distance field (orx_path_field / orx_path_query): likewise one
+# more object, with an id of its own (path_id() / orx_path_build_id())
+PATH_SRC = os.path.join(PKG_DIR, "csrc", "orx_path.hip")
+PATH_HDR = os.path.join(ROOT, "include", "orx_path.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -60,18 +64,22 @@ def hipcc() -> str:
     return "hipcc"
 
 
-def built_id(path: str = OUT):
-    """orx_build_id() of the library at `path` (None if it cannot be loaded),
+def built_ids(path: str = OUT):
+    """(orx_build_id(), orx_path_build_id()) of the library at `path` (None if
+    it cannot be loaded; the second "" for a library without orx_path.hip),
     read in a child process so this one does not map a library that a later
     build replaces."""
     code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1]); "
-            "L.orx_build_id.restype=ctypes.c_char_p; print(L.orx_build_id().decode())")
+            "L.orx_build_id.restype=ctypes.c_char_p; print(L.orx_build_id().decode()); "
+            "f=getattr(L,'orx_path_build_id',None); "
+            "f and setattr(f,'restype',ctypes.c_char_p); print(f().decode() if f else '')")
     try:
         out = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True,
                              timeout=60)
     except (OSError, subprocess.SubprocessError):
         return None
-    return out.stdout.strip() if out.returncode == 0 else None
+    lines = out.stdout.split("\n")
+    return (lines[0].strip(), lines[1].strip()) if out.returncode == 0 and len(lines) > 1 else None
 
 
 def source_id(defines: Iterable[str] = ()) -> str:
@@ -88,12 +96,30 @@ def source_id(defines: Iterable[str] = ()) -> str:
     return h.hexdigest()[:16] + ("+" + ",".join(d) if d else "")
 
 
+def path_id() -> str:
+    """The id orx_path_build_id() of a library built from these sources
+    returns: the first 16 hex digits of SHA-256(orx_path.hip || orx_path.h).
+    The distance field's two files have an id of their own, so that
+    ``source_id`` -- the engine's and the view's build id, which profiles and
+    traffic figures are keyed on -- stays the hash of the kernels they
+    measured; ``build`` rebuilds when either id differs from the tree's."""
+    h = hashlib.sha256()
+    for p in (PATH_SRC, PATH_HDR):
+        with open(p, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
+
+
+def _fresh(out: str, sid: str) -> bool:
+    return os.path.exists(out) and built_ids(out) == (sid, path_id())
+
+
 def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (),
           out: Optional[str] = None) -> str:
     defines = tuple(defines)
     out = out or (OUT if not defines else os.path.join(AB_LIBS, "custom.so"))
     sid = source_id(defines)
-    if not force and os.path.exists(out) and built_id(out) == sid:
+    if not force and _fresh(out, sid):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)
     # one build per output at a time (parallel test workers in a fresh tree):
@@ -101,18 +127,19 @@ def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (
     import fcntl
     with open(out + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
-        if not force and os.path.exists(out) and built_id(out) == sid:
+        if not force and _fresh(out, sid):
             return out
         return _build_locked(out, sid, defines, verbose)
 
 
 def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
     base = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
-            f'-DORX_BUILD_ID="{sid}"'] + [f"-D{d}" for d in defines]
+            f'-DORX_BUILD_ID="{sid}"', f'-DORX_PATH_BUILD_ID="{path_id()}"'] \
+        + [f"-D{d}" for d in defines]
     if any(d.split("=")[0] == "ORX_STAMPS" for d in defines):
         # one translation unit (the stamps buffer is a device global read back
         # by the host side, so every kernel must live in the host's unit)
-        cmd = base + ["-shared", "-o", out + ".tmp", SRC, VIEW_SRC]
+        cmd = base + ["-shared", "-o", out + ".tmp", SRC, VIEW_SRC, PATH_SRC]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -126,7 +153,8 @@ def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
 # the host side, every kernel instance declared extern; parts 1..NPARTS-1:
 # their share of the explicit instantiations, orx_engine.hip "Kernel
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
-# translation unit.  orx_view.hip (small) is one more object, compiled first.
+# translation unit.  orx_view.hip and orx_path.hip (small) are one more object
+# each, compiled last.
 NPARTS = 16
 
 
@@ -139,10 +167,12 @@ def _build_parts(base, out, verbose=False, jobs=None):
                 for k in range(NPARTS)]
         objs.append(os.path.join(tmp, "view.o"))
         cmds.append(base + ["-c", "-o", objs[-1], VIEW_SRC])
+        objs.append(os.path.join(tmp, "path.o"))
+        cmds.append(base + ["-c", "-o", objs[-1], PATH_SRC])
         if verbose:
             print(" ".join(cmds[0]) + f"  (parts 0..{NPARTS - 1}, {jobs} at a time)")
         # the heaviest parts first (the paired and one-lane rollouts)
-        order = list(range(1, NPARTS)) + [0, NPARTS]
+        order = list(range(1, NPARTS)) + [0, NPARTS, NPARTS + 1]
         running, failed = [], []
         while order or running:
             while order and len(running) < jobs:

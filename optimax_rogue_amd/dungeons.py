@@ -53,10 +53,15 @@ class DungeonBank:
 
     @classmethod
     def random(cls, width: int, height: int, n_layouts: int, seed: int = 0,
-               wall_p: float = 0.15, n_stairs: int = 1) -> "DungeonBank":
+               wall_p: float = 0.15, n_stairs: int = 1,
+               connected: bool = False) -> "DungeonBank":
         """A synthetic bank: border walls, interior walls with probability
         ``wall_p``, ``n_stairs`` staircases on Ground tiles (numpy
-        RandomState(seed); connectivity is not required by the updater)."""
+        RandomState(seed); connectivity is not required by the updater).
+        ``connected``: afterwards every Ground tile with no walkable path to
+        a staircase becomes Wall (``unreachable_ground()`` is then all zero;
+        every other tile is what ``connected=False`` draws), so no game can
+        spawn in a pocket it can only leave at ``max_ticks``."""
         rs = np.random.RandomState(seed)
         out = []
         for _ in range(int(n_layouts)):
@@ -71,10 +76,32 @@ class DungeonBank:
             for j in rs.choice(len(ground), n_stairs, replace=False):
                 t[tuple(ground[j])] = Tile.StaircaseDown
             out.append(t)
-        return cls(np.stack(out))
+        layouts = np.stack(out)
+        if connected:
+            from .path import PATH_UNREACHABLE, stair_field
+            layouts[stair_field(layouts) == PATH_UNREACHABLE] = Tile.Wall
+        return cls(layouts)
 
     def __len__(self) -> int:
         return len(self.layouts)
+
+    def stair_field(self) -> np.ndarray:
+        """uint16 [L, W, H]: every tile's walking distance to the nearest
+        StaircaseDown of its layout (``path.stair_field``: PATH_WALL on Wall
+        tiles, PATH_UNREACHABLE where no path exists); computed once."""
+        if getattr(self, "_stair_field", None) is None:
+            from .path import stair_field
+            self._stair_field = stair_field(self.layouts)
+            self._stair_field.setflags(write=False)
+        return self._stair_field
+
+    def unreachable_ground(self) -> np.ndarray:
+        """int64 [L]: per layout, the Ground tiles from which no staircase can
+        be reached -- a player spawned on one can only wait for
+        ``max_ticks``."""
+        from .path import PATH_UNREACHABLE
+        return ((self.stair_field() == PATH_UNREACHABLE)
+                & (self.layouts == Tile.Ground)).sum(axis=(1, 2))
 
     @property
     def min_ground(self) -> int:

@@ -119,6 +119,7 @@ class BatchedEngine:
         # explicit-grid dungeon generator (cfg.layouts): the bank and each
         # player's layout index; all NULL for EmptyDungeonGenerator
         self.bank = None
+        self._stair_field = None   # (the bank's distance field: made by the first path())
         if cfg.layouts is not None:
             from .dungeons import DungeonBank
             bank = DungeonBank(cfg.layouts)
@@ -481,6 +482,74 @@ class BatchedEngine:
         self._call("orx_view", int(player), int(radius), _ptr(outs[0]),
                    _ptr(outs[1]) if health else None, self.B, self._stream())
         return (outs[0], outs[1]) if health else outs[0]
+
+    @property
+    def stair_field(self):
+        """The bank's staircase distance field on the device, uint16 [L, W, H]
+        (orx_path_field, include/orx_path.h; ``DungeonBank.stair_field`` is its
+        host twin), computed by one launch at the first use -- ``__init__`` and
+        every other path keep their cost.  None without a bank."""
+        if self.bank is None:
+            return None
+        if self._stair_field is None:
+            if not hasattr(self.lib, "orx_path_field"):
+                raise RuntimeError("liborx.so has no orx_path_field -- rebuild it "
+                                   "(python -m optimax_rogue_amd.build)")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the staircase field is computed at the first path() call: "
+                                   "call path() (or read stair_field) once before capturing")
+            field = torch.empty((len(self.bank), int(self.cfg.width), int(self.cfg.height)),
+                                dtype=torch.uint16, device=self.device)
+            with torch.cuda.device(self.device):
+                code = self.lib.orx_path_field(self._pcfg, _ptr(self.bank_tiles), _ptr(field),
+                                               self._stream())
+            _lib.check("orx_path_field", code)
+            self._stair_field = field
+        return self._stair_field
+
+    def path(self, player: int = 0, radius: Optional[int] = None, out=None):
+        """orx_path_query (include/orx_path.h): how far ``player`` (0 / 1) of
+        every game is from the nearest staircase of its depth along walkable
+        cells, and the move that gets it one step closer.  Returns ``(dist,
+        move)``: int32 [n_games], -1 where no staircase can be reached, and
+        int8 [n_games], the first of Up, Right, Down, Left whose target is one
+        step closer (Stay on a staircase or where none can be reached; ready
+        as ``actions``).  With a ``radius`` (1..15) also ``window``, uint16
+        [n_games, V, V] with V = 2 * radius + 1: the distances in ``view``'s
+        geometry (PATH_WALL on walls and outside the grid, PATH_UNREACHABLE in
+        sealed pockets; optimax_rogue_amd.path).  One launch on the current
+        stream from the resident state, no host sync, no state change; with a
+        bank the first call also computes ``stair_field``.  ``out``: a
+        ``(dist, move)`` or ``(dist, move, window)`` tuple of tensors written
+        and returned instead of fresh ones.  The host reference is
+        ``path.query(self.snapshot(), ...)``."""
+        from .path import check_path_args
+        check_path_args(player, radius, self.cfg)
+        if not hasattr(self.lib, "orx_path_query"):
+            raise RuntimeError("liborx.so has no orx_path_query -- rebuild it "
+                               "(python -m optimax_rogue_amd.build)")
+        specs = [(torch.int32, (self.B,)), (torch.int8, (self.B,))]
+        if radius is not None:
+            V = 2 * int(radius) + 1
+            specs.append((torch.uint16, (self.B, V, V)))
+        if out is None:
+            outs = [torch.empty(shape, dtype=dt, device=self.device) for dt, shape in specs]
+        else:
+            outs = list(out) if isinstance(out, (tuple, list)) else [out]
+            if len(outs) != len(specs):
+                raise ValueError("out must be (dist, move), or (dist, move, window) with a radius")
+            # the kernel writes these shapes blindly: a wrong buffer would be
+            # an out-of-bounds device access, so it is refused here
+            for t, (dt, shape) in zip(outs, specs):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape \
+                        or not t.is_contiguous() or t.device != self.device:
+                    raise ValueError(f"out must hold a contiguous {dt} {shape} tensor on "
+                                     f"{self.device}")
+        field = self.stair_field
+        self._call("orx_path_query", _ptr(field), int(player), int(radius or 0), _ptr(outs[0]),
+                   _ptr(outs[1]), _ptr(outs[2]) if radius is not None else None, self.B,
+                   self._stream())
+        return tuple(outs)
 
     def _check_actions(self, a: torch.Tensor, what: str) -> None:
         # the kernels index [n_games, 2] blindly: a wrong buffer would be an

@@ -130,6 +130,24 @@ class VecEnv:
         sync).  Call it after ``step`` (or ``reset``) for that state's view."""
         return self.engine.view(radius, player=player, health=health, out=out)
 
+    def path(self, player: int = 0, radius: Optional[int] = None, out=None):
+        """``(dist, move)`` of ``player`` (0: the learner) of every game, and
+        with a ``radius`` also the uint16 distance ``window``
+        (``BatchedEngine.path``; one launch, no host sync): ``dist`` is the
+        walking distance to the nearest staircase of the player's depth (-1:
+        none can be reached), the usual potential for shaping: ``reward + c *
+        (dist_before - dist_after)`` on the steps that do not change depth."""
+        return self.engine.path(player=player, radius=radius, out=out)
+
+    def stair_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games]: for every game the move that takes ``player`` one
+        step along a shortest walkable path to a staircase (Stay where none
+        can be reached) -- ready as ``actions`` for ``step``, or as self-play's
+        second column: a scripted player that reaches the staircase on maps
+        with interior walls, where ``Policy.Staircase``'s greedy step stops at
+        the first wall in its way."""
+        return self.engine.path(player=player)[1]
+
     @staticmethod
     def outcome(before: torch.Tensor, after: torch.Tensor):
         """(reward, done) of a transition between two status tensors.  A game
