@@ -63,6 +63,8 @@ EXPORTS = ("orx_abi_version", "orx_last_error", "orx_validate_cfg", "orx_reset",
 VIEW_EXPORTS = ("orx_view",)
 # ... and of include/orx_path.h
 PATH_EXPORTS = ("orx_path_field", "orx_path_query", "orx_path_build_id")
+# ... and of include/orx_moves.h
+MOVES_EXPORTS = ("orx_moves", "orx_moves_build_id")
 
 
 def load() -> ctypes.CDLL:
@@ -155,6 +157,13 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "orx_path_build_id"):
         L.orx_path_build_id.restype = ctypes.c_char_p
         L.orx_path_build_id.argtypes = []
+    # include/orx_moves.h
+    if hasattr(L, "orx_moves"):
+        L.orx_moves.restype = ctypes.c_int
+        L.orx_moves.argtypes = [P(OrxCfg), P(OrxState), i32, vp, vp, vp, i64, vp]
+    if hasattr(L, "orx_moves_build_id"):
+        L.orx_moves_build_id.restype = ctypes.c_char_p
+        L.orx_moves_build_id.argtypes = []
     v = L.orx_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liborx.so ABI {v} != expected {ABI_VERSION}")
@@ -178,3 +187,10 @@ def path_build_id() -> str:
     sources; "" for a library built before include/orx_path.h)."""
     L = load()
     return L.orx_path_build_id().decode() if hasattr(L, "orx_path_build_id") else ""
+
+
+def moves_build_id() -> str:
+    """orx_moves_build_id() of the loaded library (build.moves_id() of its
+    sources; "" for a library built before include/orx_moves.h)."""
+    L = load()
+    return L.orx_moves_build_id().decode() if hasattr(L, "orx_moves_build_id") else ""

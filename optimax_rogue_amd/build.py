@@ -34,6 +34,10 @@ VIEW_HDR = os.path.join(ROOT, "include", "orx_view.h")
 # more object, with an id of its own (path_id() / orx_path_build_id())
 PATH_SRC = os.path.join(PKG_DIR, "csrc", "orx_path.hip")
 PATH_HDR = os.path.join(ROOT, "include", "orx_path.h")
+# what each move would do (orx_moves): one more object again, with its own id
+# (moves_id() / orx_moves_build_id())
+MOVES_SRC = os.path.join(PKG_DIR, "csrc", "orx_moves.hip")
+MOVES_HDR = os.path.join(ROOT, "include", "orx_moves.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -82,6 +86,21 @@ def built_ids(path: str = OUT):
     return (lines[0].strip(), lines[1].strip()) if out.returncode == 0 and len(lines) > 1 else None
 
 
+def built_moves_id(path: str = OUT):
+    """orx_moves_build_id() of the library at `path` ("" for a library without
+    orx_moves.hip, None if it cannot be loaded), read in a child process as
+    ``built_ids`` reads its two."""
+    code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1]); "
+            "f=getattr(L,'orx_moves_build_id',None); "
+            "f and setattr(f,'restype',ctypes.c_char_p); print(f().decode() if f else '')")
+    try:
+        out = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True,
+                             timeout=60)
+    except (OSError, subprocess.SubprocessError):
+        return None
+    return out.stdout.split("\n")[0].strip() if out.returncode == 0 else None
+
+
 def source_id(defines: Iterable[str] = ()) -> str:
     """The id orx_build_id() of a library built from these sources returns:
     the first 16 hex digits of SHA-256(orx_engine.hip || orx.h || orx_view.hip
@@ -110,8 +129,20 @@ def path_id() -> str:
     return h.hexdigest()[:16]
 
 
+def moves_id() -> str:
+    """The id orx_moves_build_id() of a library built from these sources
+    returns: the first 16 hex digits of SHA-256(orx_moves.hip ||
+    orx_moves.h); an id of its own for ``path_id``'s reason."""
+    h = hashlib.sha256()
+    for p in (MOVES_SRC, MOVES_HDR):
+        with open(p, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
+
+
 def _fresh(out: str, sid: str) -> bool:
-    return os.path.exists(out) and built_ids(out) == (sid, path_id())
+    return os.path.exists(out) and built_ids(out) == (sid, path_id()) \
+        and built_moves_id(out) == moves_id()
 
 
 def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (),
@@ -134,12 +165,13 @@ def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (
 
 def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
     base = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
-            f'-DORX_BUILD_ID="{sid}"', f'-DORX_PATH_BUILD_ID="{path_id()}"'] \
+            f'-DORX_BUILD_ID="{sid}"', f'-DORX_PATH_BUILD_ID="{path_id()}"',
+            f'-DORX_MOVES_BUILD_ID="{moves_id()}"'] \
         + [f"-D{d}" for d in defines]
     if any(d.split("=")[0] == "ORX_STAMPS" for d in defines):
         # one translation unit (the stamps buffer is a device global read back
         # by the host side, so every kernel must live in the host's unit)
-        cmd = base + ["-shared", "-o", out + ".tmp", SRC, VIEW_SRC, PATH_SRC]
+        cmd = base + ["-shared", "-o", out + ".tmp", SRC, VIEW_SRC, PATH_SRC, MOVES_SRC]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -153,8 +185,8 @@ def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
 # the host side, every kernel instance declared extern; parts 1..NPARTS-1:
 # their share of the explicit instantiations, orx_engine.hip "Kernel
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
-# translation unit.  orx_view.hip and orx_path.hip (small) are one more object
-# each, compiled last.
+# translation unit.  orx_view.hip, orx_path.hip and orx_moves.hip (small) are
+# one more object each, compiled last.
 NPARTS = 16
 
 
@@ -169,10 +201,12 @@ def _build_parts(base, out, verbose=False, jobs=None):
         cmds.append(base + ["-c", "-o", objs[-1], VIEW_SRC])
         objs.append(os.path.join(tmp, "path.o"))
         cmds.append(base + ["-c", "-o", objs[-1], PATH_SRC])
+        objs.append(os.path.join(tmp, "moves.o"))
+        cmds.append(base + ["-c", "-o", objs[-1], MOVES_SRC])
         if verbose:
             print(" ".join(cmds[0]) + f"  (parts 0..{NPARTS - 1}, {jobs} at a time)")
         # the heaviest parts first (the paired and one-lane rollouts)
-        order = list(range(1, NPARTS)) + [0, NPARTS, NPARTS + 1]
+        order = list(range(1, NPARTS)) + [0, NPARTS, NPARTS + 1, NPARTS + 2]
         running, failed = [], []
         while order or running:
             while order and len(running) < jobs:

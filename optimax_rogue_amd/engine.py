@@ -551,6 +551,61 @@ class BatchedEngine:
                    self._stream())
         return tuple(outs)
 
+    def moves(self, player: int = 0, out=None):
+        """orx_moves (include/orx_moves.h): what each move of ``player`` (0 / 1)
+        would do in every game, as ``(kind, target, amount)``: uint8, int16 and
+        int16 [n_games, MOVES_COLS = 8], column ``m`` for Move ``m`` (1..5, and
+        MOVE_HEAL with EXT_HEAL).  ``kind`` is the outcome OUT_* (REST,
+        BLOCKED, STEP, DESCEND, ATTACK_NPC, ATTACK_PLAYER, HEAL) with the
+        OUT_LETHAL / OUT_ITEM / OUT_COOLDOWN flags, ``target`` the iden an
+        attack hits (-1 otherwise), ``amount`` its damage or a heal's points
+        (optimax_rogue_amd.moves; ``moves.action_mask(kind, M)`` gives the
+        mask).  One launch on the current stream from the resident state, no
+        host sync, no state change, no random words; it can be captured in a
+        graph behind a step.  ``out``: a ``(kind, target, amount)`` tuple of
+        tensors written and returned instead of fresh ones.  The host
+        reference is ``moves.outcomes(cfg, self.snapshot(), player)``."""
+        from .moves import MOVES_COLS, check_moves_args
+        check_moves_args(player)
+        if not hasattr(self.lib, "orx_moves"):
+            raise RuntimeError("liborx.so has no orx_moves -- rebuild it "
+                               "(python -m optimax_rogue_amd.build)")
+        shape = (self.B, MOVES_COLS)
+        specs = [(torch.uint8, shape), (torch.int16, shape), (torch.int16, shape)]
+        if out is None:
+            outs = [torch.empty(shape, dtype=dt, device=self.device) for dt, shape in specs]
+        else:
+            outs = list(out) if isinstance(out, (tuple, list)) else [out]
+            if len(outs) != len(specs):
+                raise ValueError("out must be (kind, target, amount)")
+            # the kernel writes these shapes blindly, a row per vector store: a
+            # wrong buffer would be an out-of-bounds (or misaligned) device
+            # access, so it is refused here
+            for t, (dt, shape) in zip(outs, specs):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape \
+                        or not t.is_contiguous() or t.device != self.device \
+                        or t.data_ptr() % 16:
+                    raise ValueError(f"out must hold a contiguous, 16-byte aligned {dt} {shape} "
+                                     f"tensor on {self.device}")
+            if len({t.data_ptr() for t in outs}) != len(outs):
+                raise ValueError("out: kind, target and amount must be different tensors")
+        self._call("orx_moves", int(player), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), self.B,
+                   self._stream())
+        return tuple(outs)
+
+    def moves_kind(self, player: int = 0) -> torch.Tensor:
+        """``moves(player)[0]`` alone, uint8 [n_games, MOVES_COLS]: orx_moves
+        with its optional outputs NULL (what an action mask needs; a third of
+        the stores)."""
+        from .moves import MOVES_COLS, check_moves_args
+        check_moves_args(player)
+        if not hasattr(self.lib, "orx_moves"):
+            raise RuntimeError("liborx.so has no orx_moves -- rebuild it "
+                               "(python -m optimax_rogue_amd.build)")
+        kind = torch.empty((self.B, MOVES_COLS), dtype=torch.uint8, device=self.device)
+        self._call("orx_moves", int(player), _ptr(kind), None, None, self.B, self._stream())
+        return kind
+
     def _check_actions(self, a: torch.Tensor, what: str) -> None:
         # the kernels index [n_games, 2] blindly: a wrong buffer would be an
         # out-of-bounds device access, so it is refused here

@@ -139,6 +139,26 @@ class VecEnv:
         (dist_before - dist_after)`` on the steps that do not change depth."""
         return self.engine.path(player=player, radius=radius, out=out)
 
+    def moves(self, player: int = 0, out=None):
+        """``(kind, target, amount)`` of ``player`` (0: the learner) of every
+        game: what each move would do in the state as it stands -- rest,
+        blocked, step, descend, attack an NPC or the other player, heal; who
+        is hit, for how much, whether it kills, whether an item is picked up
+        (``BatchedEngine.moves``; one launch, no host sync).  Column ``m`` of
+        each [n_games, 8] tensor is Move ``m``: the per-move features of a
+        batched ``StateActionBot.evaluate``."""
+        return self.engine.moves(player=player, out=out)
+
+    def action_mask(self, player: int = 0) -> torch.Tensor:
+        """bool [n_games, M] (M = 5, or 6 with EXT_HEAL): column ``j`` is Move
+        ``j + 1``, False exactly where the updater would play a Stay in the
+        move's place (a wall or the grid's edge; with EXT_README_COMBAT an
+        attack on the other player during a cooldown).  Stay itself is always
+        allowed, so ``logits.masked_fill(~mask, -inf).argmax(1) + 1`` is a
+        valid action that is not wasted."""
+        from .moves import action_mask
+        return action_mask(self.engine.moves_kind(player), self._max_move())
+
     def stair_moves(self, player: int = 0) -> torch.Tensor:
         """int8 [n_games]: for every game the move that takes ``player`` one
         step along a shortest walkable path to a staircase (Stay where none
