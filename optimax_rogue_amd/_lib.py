@@ -52,19 +52,57 @@ class OrxError(RuntimeError):
 
 _lib = None
 
-EXPORTS = ("orx_abi_version", "orx_last_error", "orx_validate_cfg", "orx_reset", "orx_step",
-           "orx_step_events", "orx_policy", "orx_rollout", "orx_dungeon_stairs",
-           "orx_dungeon_spawn", "orx_seed_mt", "orx_build_id", "orx_rollout_lanes", "orx_dstore_depths",
-           "orx_rollout_shape", "orx_rollout_concurrent", "orx_env_step",
-           "orx_rollout_ex", "orx_env_step_ex", "orx_step_n", "orx_max_events",
-           "orx_step_n_ex", "orx_env_step_args")
-# the entry points of include/orx_view.h (a header of its own: EXPORTS is
-# exactly what orx.h declares)
-VIEW_EXPORTS = ("orx_view",)
-# ... and of include/orx_path.h
-PATH_EXPORTS = ("orx_path_field", "orx_path_query", "orx_path_build_id")
-# ... and of include/orx_moves.h
-MOVES_EXPORTS = ("orx_moves", "orx_moves_build_id")
+vp, i64, i32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
+_int, _str = ctypes.c_int, ctypes.c_char_p
+_cfg, _st = ctypes.POINTER(OrxCfg), ctypes.POINTER(OrxState)
+
+# name -> (restype, argtypes), one table per header.  include/orx.h: what
+# every library has ...
+_REQUIRED = {
+    "orx_abi_version": (_int, []),
+    "orx_last_error": (_str, []),
+    "orx_validate_cfg": (_int, [_cfg]),
+    "orx_reset": (_int, [_cfg, _st, vp, i64, u64, i64, vp]),
+    "orx_step": (_int, [_cfg, _st, vp, i64, u64, i64, vp]),
+    "orx_step_events": (_int, [_cfg, _st, vp, vp, vp, i64, u64, i64, vp]),
+    "orx_policy": (_int, [_cfg, _st, i32, i32, vp, i64, u64, i64, vp]),
+    "orx_rollout": (_int, [_cfg, _st, i32, i32, i32, vp, vp, i64, u64, i64, vp]),
+    "orx_dungeon_stairs": (_int, [_cfg, vp, vp, vp, vp, vp, vp, i64, u64, vp]),
+    "orx_dungeon_spawn": (_int, [_cfg, _st, vp, vp, vp, vp, vp, vp, vp, i64, u64, vp]),
+    "orx_seed_mt": (_int, [_cfg, _st, i64, u64, i64, vp]),
+    "orx_build_id": (_str, []),
+    "orx_rollout_lanes": (_int, [i64]),
+}
+# ... and what is bound only when present (an A/B diagnostic may load an older build)
+_OPTIONAL = {
+    "orx_dstore_depths": (_int, [_cfg]),
+    "orx_rollout_shape": (_int, [_cfg, i32, i32, i64, i32, i32, ctypes.POINTER(OrxRolloutShape)]),
+    "orx_rollout_concurrent": (_int, [_cfg, _st, i32, i32, i32, vp, vp, i64, u64, i64, i32, vp]),
+    "orx_env_step": (_int, [_cfg, _st, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, u64, i64, vp]),
+    "orx_rollout_ex": (_int, [_cfg, _st, i32, i32, i32, vp, vp, i32, i64, u64, i64, i32, vp]),
+    "orx_env_step_ex": (_int, [_cfg, _st, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, u64, i64,
+                               vp]),
+    "orx_step_n": (_int, [_cfg, _st, vp, i32, vp, i32, i64, u64, i64, vp]),
+    "orx_max_events": (_int, [_cfg]),
+    "orx_step_n_ex": (_int, [_cfg, _st, vp, i32, vp, i32, i64, u64, i64, i32, vp]),
+    "orx_env_step_args": (_int, [ctypes.POINTER(OrxEnvStepArgs)]),
+}
+# include/orx_view.h, orx_path.h, orx_moves.h (EXPORTS is orx.h alone); optional too
+_VIEW = {"orx_view": (_int, [_cfg, _st, i32, i32, vp, vp, i64, vp])}
+_PATH = {
+    "orx_path_field": (_int, [_cfg, vp, vp, vp]),
+    "orx_path_query": (_int, [_cfg, _st, vp, i32, i32, vp, vp, vp, i64, vp]),
+    "orx_path_build_id": (_str, []),
+}
+_MOVES = {
+    "orx_moves": (_int, [_cfg, _st, i32, vp, vp, vp, i64, vp]),
+    "orx_moves_build_id": (_str, []),
+}
+
+EXPORTS = tuple(_REQUIRED) + tuple(_OPTIONAL)
+VIEW_EXPORTS = tuple(_VIEW)
+PATH_EXPORTS = tuple(_PATH)
+MOVES_EXPORTS = tuple(_MOVES)
 
 
 def load() -> ctypes.CDLL:
@@ -78,92 +116,11 @@ def load() -> ctypes.CDLL:
         raise RuntimeError(f"HIP engine library missing: {LIB_PATH} -- run "
                            "`python -m optimax_rogue_amd.build` first")
     L = ctypes.CDLL(LIB_PATH)
-    vp, i64, i32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
-    P = ctypes.POINTER
-    L.orx_abi_version.restype = ctypes.c_int
-    L.orx_abi_version.argtypes = []
-    L.orx_last_error.restype = ctypes.c_char_p
-    L.orx_last_error.argtypes = []
-    L.orx_validate_cfg.restype = ctypes.c_int
-    L.orx_validate_cfg.argtypes = [P(OrxCfg)]
-    L.orx_reset.restype = ctypes.c_int
-    L.orx_reset.argtypes = [P(OrxCfg), P(OrxState), vp, i64, u64, i64, vp]
-    L.orx_step.restype = ctypes.c_int
-    L.orx_step.argtypes = [P(OrxCfg), P(OrxState), vp, i64, u64, i64, vp]
-    L.orx_step_events.restype = ctypes.c_int
-    L.orx_step_events.argtypes = [P(OrxCfg), P(OrxState), vp, vp, vp, i64, u64, i64, vp]
-    L.orx_policy.restype = ctypes.c_int
-    L.orx_policy.argtypes = [P(OrxCfg), P(OrxState), i32, i32, vp, i64, u64, i64, vp]
-    L.orx_rollout.restype = ctypes.c_int
-    L.orx_rollout.argtypes = [P(OrxCfg), P(OrxState), i32, i32, i32, vp, vp, i64, u64, i64, vp]
-    L.orx_dungeon_stairs.restype = ctypes.c_int
-    L.orx_dungeon_stairs.argtypes = [P(OrxCfg), vp, vp, vp, vp, vp, vp, i64, u64, vp]
-    L.orx_dungeon_spawn.restype = ctypes.c_int
-    L.orx_dungeon_spawn.argtypes = [P(OrxCfg), P(OrxState), vp, vp, vp, vp, vp, vp, vp, i64, u64,
-                                    vp]
-    L.orx_seed_mt.restype = ctypes.c_int
-    L.orx_seed_mt.argtypes = [P(OrxCfg), P(OrxState), i64, u64, i64, vp]
-    L.orx_build_id.restype = ctypes.c_char_p
-    L.orx_build_id.argtypes = []
-    L.orx_rollout_lanes.restype = ctypes.c_int
-    L.orx_rollout_lanes.argtypes = [i64]
-    # (bound only when present: an A/B diagnostic may load an older build)
-    if hasattr(L, "orx_rollout_shape"):
-        L.orx_rollout_shape.restype = ctypes.c_int
-        L.orx_rollout_shape.argtypes = [P(OrxCfg), i32, i32, i64, i32, i32, P(OrxRolloutShape)]
-    if hasattr(L, "orx_rollout_concurrent"):
-        L.orx_rollout_concurrent.restype = ctypes.c_int
-        L.orx_rollout_concurrent.argtypes = [P(OrxCfg), P(OrxState), i32, i32, i32, vp, vp, i64,
-                                             u64, i64, i32, vp]
-    if hasattr(L, "orx_rollout_ex"):
-        L.orx_rollout_ex.restype = ctypes.c_int
-        L.orx_rollout_ex.argtypes = [P(OrxCfg), P(OrxState), i32, i32, i32, vp, vp, i32, i64, u64,
-                                     i64, i32, vp]
-    if hasattr(L, "orx_env_step"):
-        L.orx_env_step.restype = ctypes.c_int
-        L.orx_env_step.argtypes = [P(OrxCfg), P(OrxState), vp, i32, i32, i32, vp, vp, vp, vp, vp,
-                                   i64, u64, i64, vp]
-    if hasattr(L, "orx_env_step_ex"):
-        L.orx_env_step_ex.restype = ctypes.c_int
-        L.orx_env_step_ex.argtypes = [P(OrxCfg), P(OrxState), vp, i32, i32, i32, vp, vp, vp, vp,
-                                      vp, vp, i64, u64, i64, vp]
-    if hasattr(L, "orx_env_step_args"):
-        L.orx_env_step_args.restype = ctypes.c_int
-        L.orx_env_step_args.argtypes = [P(OrxEnvStepArgs)]
-    if hasattr(L, "orx_step_n"):
-        L.orx_step_n.restype = ctypes.c_int
-        L.orx_step_n.argtypes = [P(OrxCfg), P(OrxState), vp, i32, vp, i32, i64, u64, i64, vp]
-    if hasattr(L, "orx_step_n_ex"):
-        L.orx_step_n_ex.restype = ctypes.c_int
-        L.orx_step_n_ex.argtypes = [P(OrxCfg), P(OrxState), vp, i32, vp, i32, i64, u64, i64, i32,
-                                    vp]
-    if hasattr(L, "orx_max_events"):
-        L.orx_max_events.restype = ctypes.c_int
-        L.orx_max_events.argtypes = [P(OrxCfg)]
-    if hasattr(L, "orx_dstore_depths"):
-        L.orx_dstore_depths.restype = ctypes.c_int
-        L.orx_dstore_depths.argtypes = [P(OrxCfg)]
-    # include/orx_view.h
-    if hasattr(L, "orx_view"):
-        L.orx_view.restype = ctypes.c_int
-        L.orx_view.argtypes = [P(OrxCfg), P(OrxState), i32, i32, vp, vp, i64, vp]
-    # include/orx_path.h
-    if hasattr(L, "orx_path_field"):
-        L.orx_path_field.restype = ctypes.c_int
-        L.orx_path_field.argtypes = [P(OrxCfg), vp, vp, vp]
-    if hasattr(L, "orx_path_query"):
-        L.orx_path_query.restype = ctypes.c_int
-        L.orx_path_query.argtypes = [P(OrxCfg), P(OrxState), vp, i32, i32, vp, vp, vp, i64, vp]
-    if hasattr(L, "orx_path_build_id"):
-        L.orx_path_build_id.restype = ctypes.c_char_p
-        L.orx_path_build_id.argtypes = []
-    # include/orx_moves.h
-    if hasattr(L, "orx_moves"):
-        L.orx_moves.restype = ctypes.c_int
-        L.orx_moves.argtypes = [P(OrxCfg), P(OrxState), i32, vp, vp, vp, i64, vp]
-    if hasattr(L, "orx_moves_build_id"):
-        L.orx_moves_build_id.restype = ctypes.c_char_p
-        L.orx_moves_build_id.argtypes = []
+    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES):
+        for name, (restype, argtypes) in table.items():
+            if table is _REQUIRED or hasattr(L, name):   # (a missing required symbol raises)
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
     v = L.orx_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liborx.so ABI {v} != expected {ABI_VERSION}")

@@ -21,23 +21,24 @@ import hashlib
 import os
 import subprocess
 import sys
+from collections import namedtuple
+from pathlib import Path
 from typing import Iterable, Optional
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 SRC = os.path.join(PKG_DIR, "csrc", "orx_engine.hip")
 HDR = os.path.join(ROOT, "include", "orx.h")
-# the egocentric map view (orx_view): one more object of the library
+# the queries, one more object of the library each: the egocentric map view
+# (orx_view), the staircase distance field (orx_path_*), what each move would
+# do (orx_moves), and what the three share (internal, hashed into every id)
 VIEW_SRC = os.path.join(PKG_DIR, "csrc", "orx_view.hip")
 VIEW_HDR = os.path.join(ROOT, "include", "orx_view.h")
-# the staircase distance field (orx_path_field / orx_path_query): likewise one
-# more object, with an id of its own (path_id() / orx_path_build_id())
 PATH_SRC = os.path.join(PKG_DIR, "csrc", "orx_path.hip")
 PATH_HDR = os.path.join(ROOT, "include", "orx_path.h")
-# what each move would do (orx_moves): one more object again, with its own id
-# (moves_id() / orx_moves_build_id())
 MOVES_SRC = os.path.join(PKG_DIR, "csrc", "orx_moves.hip")
 MOVES_HDR = os.path.join(ROOT, "include", "orx_moves.h")
+QUERY_HDR = os.path.join(PKG_DIR, "csrc", "orx_query.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -61,6 +62,21 @@ VARIANTS = {
 }
 
 
+# The library's parts, each with a build id of its own: the C function that
+# returns it, the -D macro that carries it into the build, the files it hashes
+# (in this order), the sources compiled.  Ids, flags and compile list come from here.
+Part = namedtuple("Part", "symbol macro files sources")
+PARTS = {
+    "engine": Part("orx_build_id", "ORX_BUILD_ID", (SRC, HDR, VIEW_SRC, VIEW_HDR, QUERY_HDR),
+                   (SRC, VIEW_SRC)),
+    "path": Part("orx_path_build_id", "ORX_PATH_BUILD_ID", (PATH_SRC, PATH_HDR, QUERY_HDR),
+                 (PATH_SRC,)),
+    "moves": Part("orx_moves_build_id", "ORX_MOVES_BUILD_ID", (MOVES_SRC, MOVES_HDR, QUERY_HDR),
+                  (MOVES_SRC,)),
+}
+SOURCES = [src for p in PARTS.values() for src in p.sources]   # (SRC first: _build_parts splits it)
+
+
 def hipcc() -> str:
     for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc"), "hipcc"):
         if os.path.sep not in c or os.path.exists(c):
@@ -68,89 +84,60 @@ def hipcc() -> str:
     return "hipcc"
 
 
-def built_ids(path: str = OUT):
-    """(orx_build_id(), orx_path_build_id()) of the library at `path` (None if
-    it cannot be loaded; the second "" for a library without orx_path.hip),
-    read in a child process so this one does not map a library that a later
-    build replaces."""
-    code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1]); "
-            "L.orx_build_id.restype=ctypes.c_char_p; print(L.orx_build_id().decode()); "
-            "f=getattr(L,'orx_path_build_id',None); "
-            "f and setattr(f,'restype',ctypes.c_char_p); print(f().decode() if f else '')")
-    try:
-        out = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True,
-                             timeout=60)
-    except (OSError, subprocess.SubprocessError):
-        return None
-    lines = out.stdout.split("\n")
-    return (lines[0].strip(), lines[1].strip()) if out.returncode == 0 and len(lines) > 1 else None
-
-
-def built_moves_id(path: str = OUT):
-    """orx_moves_build_id() of the library at `path` ("" for a library without
-    orx_moves.hip, None if it cannot be loaded), read in a child process as
-    ``built_ids`` reads its two."""
-    code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1]); "
-            "f=getattr(L,'orx_moves_build_id',None); "
-            "f and setattr(f,'restype',ctypes.c_char_p); print(f().decode() if f else '')")
-    try:
-        out = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True,
-                             timeout=60)
-    except (OSError, subprocess.SubprocessError):
-        return None
-    return out.stdout.split("\n")[0].strip() if out.returncode == 0 else None
+def tree_ids(defines: Iterable[str] = ()) -> dict:
+    """The ids of a library built from this tree, by part name: the first 16
+    hex digits of SHA-256 over the part's files, and for the engine of a build
+    with extra definitions ``+`` and their sorted list (its own id, then)."""
+    ids = {name: hashlib.sha256(b"".join(Path(p).read_bytes() for p in part.files)).hexdigest()[:16]
+           for name, part in PARTS.items()}
+    d = sorted(defines)
+    ids["engine"] += "+" + ",".join(d) if d else ""
+    return ids
 
 
 def source_id(defines: Iterable[str] = ()) -> str:
-    """The id orx_build_id() of a library built from these sources returns:
-    the first 16 hex digits of SHA-256(orx_engine.hip || orx.h || orx_view.hip
-    || orx_view.h), and for a
-    build with extra definitions ``+`` and their sorted list (so the product
-    id is exactly the sources' hash and no diagnostic build shares it)."""
-    h = hashlib.sha256()
-    for p in (SRC, HDR, VIEW_SRC, VIEW_HDR):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    d = sorted(defines)
-    return h.hexdigest()[:16] + ("+" + ",".join(d) if d else "")
+    """What orx_build_id() of a library built from these sources returns."""
+    return tree_ids(defines)["engine"]
 
 
 def path_id() -> str:
-    """The id orx_path_build_id() of a library built from these sources
-    returns: the first 16 hex digits of SHA-256(orx_path.hip || orx_path.h).
-    The distance field's two files have an id of their own, so that
-    ``source_id`` -- the engine's and the view's build id, which profiles and
-    traffic figures are keyed on -- stays the hash of the kernels they
-    measured; ``build`` rebuilds when either id differs from the tree's."""
-    h = hashlib.sha256()
-    for p in (PATH_SRC, PATH_HDR):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
+    """What orx_path_build_id() of a library built from these sources returns."""
+    return tree_ids()["path"]
 
 
 def moves_id() -> str:
-    """The id orx_moves_build_id() of a library built from these sources
-    returns: the first 16 hex digits of SHA-256(orx_moves.hip ||
-    orx_moves.h); an id of its own for ``path_id``'s reason."""
-    h = hashlib.sha256()
-    for p in (MOVES_SRC, MOVES_HDR):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
+    """What orx_moves_build_id() of a library built from these sources returns."""
+    return tree_ids()["moves"]
 
 
-def _fresh(out: str, sid: str) -> bool:
-    return os.path.exists(out) and built_ids(out) == (sid, path_id()) \
-        and built_moves_id(out) == moves_id()
+def built_ids(path: str = OUT):
+    """``tree_ids``'s dict for the library at `path` ("" for a part it was built
+    without; None if it cannot be loaded), read in one child process so this
+    one does not map a library that a later build replaces."""
+    code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1])\n"
+            "for f in (getattr(L,s,None) for s in sys.argv[2:]):\n"
+            "    f and setattr(f,'restype',ctypes.c_char_p); print(f().decode() if f else '')")
+    cmd = [sys.executable, "-c", code, path] + [p.symbol for p in PARTS.values()]
+    try:
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=60)
+    except (OSError, subprocess.SubprocessError):
+        return None
+    lines = out.stdout.split("\n")
+    if out.returncode != 0 or len(lines) <= len(PARTS):
+        return None
+    return {name: line.strip() for name, line in zip(PARTS, lines)}
+
+
+def _fresh(out: str, ids: dict) -> bool:
+    return os.path.exists(out) and built_ids(out) == ids
 
 
 def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (),
           out: Optional[str] = None) -> str:
     defines = tuple(defines)
     out = out or (OUT if not defines else os.path.join(AB_LIBS, "custom.so"))
-    sid = source_id(defines)
-    if not force and _fresh(out, sid):
+    ids = tree_ids(defines)
+    if not force and _fresh(out, ids):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)
     # one build per output at a time (parallel test workers in a fresh tree):
@@ -158,20 +145,19 @@ def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (
     import fcntl
     with open(out + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
-        if not force and _fresh(out, sid):
+        if not force and _fresh(out, ids):
             return out
-        return _build_locked(out, sid, defines, verbose)
+        return _build_locked(out, ids, defines, verbose)
 
 
-def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
-    base = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
-            f'-DORX_BUILD_ID="{sid}"', f'-DORX_PATH_BUILD_ID="{path_id()}"',
-            f'-DORX_MOVES_BUILD_ID="{moves_id()}"'] \
+def _build_locked(out: str, ids: dict, defines, verbose: bool) -> str:
+    base = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall"] \
+        + [f'-D{p.macro}="{ids[name]}"' for name, p in PARTS.items()] \
         + [f"-D{d}" for d in defines]
     if any(d.split("=")[0] == "ORX_STAMPS" for d in defines):
         # one translation unit (the stamps buffer is a device global read back
         # by the host side, so every kernel must live in the host's unit)
-        cmd = base + ["-shared", "-o", out + ".tmp", SRC, VIEW_SRC, PATH_SRC, MOVES_SRC]
+        cmd = base + ["-shared", "-o", out + ".tmp"] + SOURCES
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -185,8 +171,8 @@ def _build_locked(out: str, sid: str, defines, verbose: bool) -> str:
 # the host side, every kernel instance declared extern; parts 1..NPARTS-1:
 # their share of the explicit instantiations, orx_engine.hip "Kernel
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
-# translation unit.  orx_view.hip, orx_path.hip and orx_moves.hip (small) are
-# one more object each, compiled last.
+# translation unit.  The other SOURCES (orx_view.hip, orx_path.hip and
+# orx_moves.hip: small) are one more object each, compiled last.
 NPARTS = 16
 
 
@@ -197,16 +183,13 @@ def _build_parts(base, out, verbose=False, jobs=None):
         objs = [os.path.join(tmp, f"part{k}.o") for k in range(NPARTS)]
         cmds = [base + ["-c", f"-DORX_NPARTS={NPARTS}", f"-DORX_PART={k}", "-o", objs[k], SRC]
                 for k in range(NPARTS)]
-        objs.append(os.path.join(tmp, "view.o"))
-        cmds.append(base + ["-c", "-o", objs[-1], VIEW_SRC])
-        objs.append(os.path.join(tmp, "path.o"))
-        cmds.append(base + ["-c", "-o", objs[-1], PATH_SRC])
-        objs.append(os.path.join(tmp, "moves.o"))
-        cmds.append(base + ["-c", "-o", objs[-1], MOVES_SRC])
+        for src in SOURCES[1:]:
+            objs.append(os.path.join(tmp, os.path.basename(src)[:-len(".hip")] + ".o"))
+            cmds.append(base + ["-c", "-o", objs[-1], src])
         if verbose:
             print(" ".join(cmds[0]) + f"  (parts 0..{NPARTS - 1}, {jobs} at a time)")
         # the heaviest parts first (the paired and one-lane rollouts)
-        order = list(range(1, NPARTS)) + [0, NPARTS, NPARTS + 1, NPARTS + 2]
+        order = list(range(1, NPARTS)) + [0] + list(range(NPARTS, len(cmds)))
         running, failed = [], []
         while order or running:
             while order and len(running) < jobs:

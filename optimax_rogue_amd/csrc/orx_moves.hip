@@ -24,21 +24,13 @@
 //     255), and the slot's alive bit and health only where a target is hit;
 //   items: the on-floor slots are scanned only in games that have any.
 // Plain C++ and vector stores only.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
 #include "../../include/orx_moves.h"
-
-// the host side's error path (orx_engine.hip, "Host side of the C-ABI")
-namespace orx_dev {
-int fail(int code, const char* msg);
-int launch_status(const char* what);
-}  // namespace orx_dev
+#include "orx_query.h"
 
 namespace orx_moves_dev {
 
-constexpr int kBlock = 256;
+using namespace orx_query;
+
 constexpr uint32_t kNoCell = 0xFFFFFFFFu;  // the packed key of a target outside the grid
 
 struct MovesArgs {
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(kBlock) void moves_kernel(const MovesArgs a) {
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (b >= B) return;
   const int W = a.W, H = a.H, K = a.K;
-  const int64_t me = (int64_t)a.player * B + b, ot = (int64_t)(1 - a.player) * B + b;
+  const auto [me, ot] = player_rows(a.player, B, b);
 
   // the game's header: both players (coalesced rows)
   const int32_t x = a.p_x[me], y = a.p_y[me], d = a.p_depth[me], hp = a.p_health[me];
@@ -94,9 +86,8 @@ __global__ __launch_bounds__(kBlock) void moves_kernel(const MovesArgs a) {
       key[j] = in ? (uint32_t)tx[j] | (uint32_t)ty[j] << 8 : kNoCell;
     }
   } else {
-    int32_t lay = a.p_layout[me];  // (clamped: the tile lookup must stay inside the bank)
-    lay = lay < 0 ? 0 : lay >= a.L ? a.L - 1 : lay;
-    const uint8_t* bt = a.bank_tiles + (size_t)lay * ((size_t)W * (size_t)H);
+    const uint8_t* bt =
+        a.bank_tiles + (size_t)clamp_layout(a.p_layout[me], a.L) * ((size_t)W * (size_t)H);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const bool in = tx[j] >= 0 && tx[j] < W && ty[j] >= 0 && ty[j] < H;
@@ -227,32 +218,20 @@ extern "C" int orx_moves(const orx_cfg_t* cfg, const orx_state_t* st, int32_t pl
                          int16_t* target, int16_t* amount, int64_t n_games, void* stream) {
   using namespace orx_moves_dev;
   using orx_dev::fail;
-  if (const int r = orx_validate_cfg(cfg)) return r;
-  if (player != 0 && player != 1) return fail(ORX_EINVAL, "orx_moves: player must be 0 or 1");
+  int r;
+  if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_moves", player))) return r;
   if (!kind) return fail(ORX_EINVAL, "orx_moves: kind is NULL");
-  if (n_games <= 0 || n_games > 0x7FFFFFFFLL) return fail(ORX_EINVAL, "orx_moves: bad n_games");
+  if ((r = check_games("orx_moves", n_games))) return r;
   // (a row is one vector store)
   if ((reinterpret_cast<uintptr_t>(kind) & 7) || (reinterpret_cast<uintptr_t>(target) & 15) ||
       (reinterpret_cast<uintptr_t>(amount) & 15))
     return fail(ORX_EINVAL, "orx_moves: kind must be 8-byte, target and amount 16-byte aligned");
-  if (!st) return fail(ORX_EINVAL, "state is NULL");
-  if (!st->p_x || !st->p_y || !st->p_depth || !st->p_health)
-    return fail(ORX_EINVAL, "a required state pointer is NULL");
-  if (cfg->n_layouts == 0 && (!st->st_x || !st->st_y))
-    return fail(ORX_EINVAL, "n_layouts == 0 needs st_x and st_y");
-  if (cfg->n_layouts > 0 && (!st->p_layout || !st->bank_tiles))
-    return fail(ORX_EINVAL, "n_layouts > 0 needs p_layout and bank_tiles");
-  if (cfg->n_npcs > 0 && (!st->npc_pos || !st->npc_health || !st->npc_alive))
-    return fail(ORX_EINVAL, "n_npcs > 0 needs npc_pos, npc_health and npc_alive");
-  if (cfg->n_npcs > ORX_MAX_REG_NPCS && !st->npc_grid)
-    return fail(ORX_EINVAL, "n_npcs > 16 needs npc_grid ([B][W * H] uint8)");
-  const bool character = (cfg->flags & ORX_EXT_CHARACTER) != 0;
-  if (character && !st->p_rpg) return fail(ORX_EINVAL, "the character mechanics need p_rpg");
+  if ((r = check_state(cfg, st, kPlayers | kStairsNoBank | kBank | kNpcs | kGrid | kCharacter |
+                                    kItems)))
+    return r;
   // (orx_validate_cfg holds ORX_EXT_ITEMS to n_npcs <= ORX_MAX_REG_NPCS: the
   // on-floor bits are one word)
-  const bool items = (cfg->flags & ORX_EXT_ITEMS) && cfg->n_npcs > 0 && cfg->n_npcs <= 32;
-  if (items && (!st->item_pos || !st->item_mask))
-    return fail(ORX_EINVAL, "ORX_EXT_ITEMS needs item_pos and item_mask");
+  const bool character = (cfg->flags & ORX_EXT_CHARACTER) != 0, items = has_items(cfg);
 
   MovesArgs a;
   a.p_x = st->p_x, a.p_y = st->p_y, a.p_depth = st->p_depth, a.p_health = st->p_health;
@@ -265,7 +244,7 @@ extern "C" int orx_moves(const orx_cfg_t* cfg, const orx_state_t* st, int32_t pl
   a.B = n_games;
   a.W = cfg->width, a.H = cfg->height, a.K = cfg->n_npcs, a.L = cfg->n_layouts;
   a.player = player;
-  a.npc_depth = cfg->start_mode == ORX_START_SEPARATED ? cfg->p1_depth : 0;
+  a.npc_depth = npc_depth(cfg);
   a.flags = cfg->flags;
   a.damage = cfg->player_damage, a.armor = cfg->player_armor;
   a.mana_third = cfg->mana_max / 3;

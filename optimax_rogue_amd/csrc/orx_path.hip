@@ -24,9 +24,10 @@
 //      slice does not start or end 16-byte aligned).
 //
 // query: point_kernel (no window) is one lane per game and five values.
-// window_kernel follows view_kernel (orx_view.hip): a workgroup of 256
-// threads owns G consecutive games (64, 32 or 16: the most whose tile stays
-// within kTileBudget), stages their headers in LDS, builds the G x V*V uint16
+// window_kernel has view_kernel's shape, from the same pieces (orx_query.h:
+// the window, its split, stream_out): a workgroup of 256 threads owns G
+// consecutive games (64, 32 or 16: the most whose tile stays within
+// kTileBudget), stages their headers in LDS, builds the G x V*V uint16
 // tile in LDS -- the closed form eight cells per thread with one aligned
 // 16-byte LDS store; a bank 16 or 32 neighbouring lanes per window column,
 // because a fixed x with consecutive y is consecutive uint16 in the field (a
@@ -34,19 +35,12 @@
 // from the tile's centre cells, and streams the tile's contiguous bytes out
 // 16 per lane.
 // Plain C++ and vector stores only.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
 #include "../../include/orx_path.h"
-
-// the host side's error path (orx_engine.hip, "Host side of the C-ABI")
-namespace orx_dev {
-int fail(int code, const char* msg);
-int launch_status(const char* what);
-}  // namespace orx_dev
+#include "orx_query.h"
 
 namespace orx_path_dev {
+
+using namespace orx_query;
 
 constexpr uint32_t kWall = ORX_PATH_WALL, kFar = ORX_PATH_UNREACHABLE;
 
@@ -160,9 +154,6 @@ __global__ __launch_bounds__(kFieldBlock) void field_kernel(const FieldArgs a) {
 // ---------------------------------------------------------------------------
 // the query
 // ---------------------------------------------------------------------------
-constexpr int kBlock = 256;
-constexpr int kTileBudget = 40 * 1024;  // LDS bytes of a workgroup's tile
-
 // header fields staged per game ([kHdr][G] int32 in LDS)
 enum { H_PX, H_PY, H_SX, H_SY, H_LAYOUT, kHdr };
 
@@ -175,7 +166,7 @@ struct PathArgs {
   uint16_t* window;
   int64_t B;
   int32_t W, H, L, R, G, player;
-  uint32_t inv_vv, inv_v;  // 2^32 / (V * V) + 1 and 2^32 / V + 1: __umulhi(n, inv) = n / d for n < 2^16
+  uint32_t inv_vv, inv_v;  // (R, G, inv_vv, inv_v: a Window, with `window`)
 };
 
 // the value of cell (x, y): `f` is the layout's plane of a bank (a.L > 0),
@@ -202,22 +193,16 @@ __device__ __forceinline__ int8_t move_of(uint32_t own, uint32_t up, uint32_t ri
          : left == want ? ORX_MOVE_LEFT : ORX_MOVE_STAY;
 }
 
-__device__ __forceinline__ int clamp_layout(const PathArgs& a, int64_t me) {
-  if (a.L <= 0) return 0;
-  const int lay = a.p_layout[me];
-  return lay < 0 ? 0 : lay >= a.L ? a.L - 1 : lay;
-}
-
 // no window: one lane per game, five values
 __global__ __launch_bounds__(kBlock) void point_kernel(const PathArgs a) {
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (b >= a.B) return;
-  const int64_t me = (int64_t)a.player * a.B + b;
+  const int64_t me = player_rows(a.player, a.B, b).me;
   const int x = a.p_x[me], y = a.p_y[me];
   int sx = 0, sy = 0;
   const uint16_t* f = nullptr;
   if (a.L > 0) {
-    f = a.field + (size_t)clamp_layout(a, me) * (size_t)(a.W * a.H);
+    f = a.field + (size_t)layout_of(a, me) * (size_t)(a.W * a.H);
   } else {
     sx = a.st_x[me], sy = a.st_y[me];
   }
@@ -228,20 +213,10 @@ __global__ __launch_bounds__(kBlock) void point_kernel(const PathArgs a) {
                         value_at(a, f, x, y + 1, sx, sy), value_at(a, f, x - 1, y, sx, sy));
 }
 
-// tile[0 .. n) (uint16 in LDS, 16-byte aligned) -> out[0 .. n): 16 bytes per
-// lane while the destination is 16-byte aligned, the rest (and everything, for
-// a destination that is not) one uint16 at a time
-__device__ __forceinline__ void stream_out(const uint16_t* tile, uint16_t* out, int n, int t) {
-  const int nvec = ((reinterpret_cast<uintptr_t>(out) & 15) == 0) ? n >> 3 : 0;
-  const uint4* src = reinterpret_cast<const uint4*>(tile);
-  uint4* dst = reinterpret_cast<uint4*>(out);
-  for (int v = t; v < nvec; v += kBlock) dst[v] = src[v];
-  for (int i = (nvec << 3) + t; i < n; i += kBlock) out[i] = tile[i];
-}
-
 __global__ __launch_bounds__(kBlock) void window_kernel(const PathArgs a) {
   extern __shared__ uint4 smem[];
-  const int G = a.G, R = a.R, V = 2 * R + 1, VV = V * V, H = a.H;
+  const Window win = Window::of(a.R, a.G, a.inv_vv, a.inv_v);
+  const int G = win.G, R = win.R, V = win.V, VV = win.VV, H = a.H;
   uint16_t* tile = reinterpret_cast<uint16_t*>(smem);  // G * VV uint16 (G % 8 == 0: whole uint4s)
   int32_t* hdr = reinterpret_cast<int32_t*>(tile + G * VV);
   const int64_t B = a.B;
@@ -251,12 +226,12 @@ __global__ __launch_bounds__(kBlock) void window_kernel(const PathArgs a) {
 
   // 1. the games' headers, coalesced over the games
   if (t < nb) {
-    const int64_t me = (int64_t)a.player * B + b0 + t;
+    const int64_t me = player_rows(a.player, B, b0 + t).me;
     hdr[H_PX * G + t] = a.p_x[me];
     hdr[H_PY * G + t] = a.p_y[me];
     hdr[H_SX * G + t] = a.L > 0 ? 0 : a.st_x[me];
     hdr[H_SY * G + t] = a.L > 0 ? 0 : a.st_y[me];
-    hdr[H_LAYOUT * G + t] = clamp_layout(a, me);
+    hdr[H_LAYOUT * G + t] = layout_of(a, me);
   }
   __syncthreads();
 
@@ -270,11 +245,8 @@ __global__ __launch_bounds__(kBlock) void window_kernel(const PathArgs a) {
     const int nvec = (nb * VV + 7) >> 3;
     const uint32_t W2 = (uint32_t)(a.W - 2), H2 = (uint32_t)(H - 2);  // interior: 1 .. W - 2
     for (int v = t; v < nvec; v += kBlock) {
-      const uint32_t c = (uint32_t)v << 3;
-      int g = (int)__umulhi(c, a.inv_vv);  // c / VV (exact: c < 2^16)
-      const uint32_t r = c - (uint32_t)(g * VV);
-      int j = (int)__umulhi(r, a.inv_v);   // r / V
-      int i = (int)r - j * V;
+      const Window::Cell first = win.split((uint32_t)v << 3);
+      int g = first.g, j = first.j, i = first.i;
       int x0 = 0, sx = 0, ady = 0;
       bool yin = false;
       auto row = [&]() {
@@ -310,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void window_kernel(const PathArgs a) {
     const int shift = V <= 16 ? 4 : 5, j = t & ((1 << shift) - 1);
     if (j < V) {
       for (int col = t >> shift; col < cols; col += kBlock >> shift) {
-        const int g = (int)__umulhi((uint32_t)col, a.inv_v), i = col - g * V;
+        const int g = win.div_v((uint32_t)col), i = col - g * V;
         const int x = hdr[H_PX * G + g] + i - R, y = hdr[H_PY * G + g] + j - R;
         uint16_t val = (uint16_t)kWall;
         if ((uint32_t)x < (uint32_t)a.W && (uint32_t)y < (uint32_t)H)
@@ -378,24 +350,21 @@ extern "C" int orx_path_query(const orx_cfg_t* cfg, const orx_state_t* st, const
                               uint16_t* window, int64_t n_games, void* stream) {
   using namespace orx_path_dev;
   using orx_dev::fail;
-  if (const int r = orx_validate_cfg(cfg)) return r;
-  if (player != 0 && player != 1) return fail(ORX_EINVAL, "orx_path_query: player must be 0 or 1");
+  int r;
+  if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_path_query", player))) return r;
   if (!dist && !move && !window)
     return fail(ORX_EINVAL, "orx_path_query: dist, move and window are all NULL");
   if (window && (radius < 1 || radius > ORX_VIEW_MAX_RADIUS))
     return fail(ORX_EINVAL, "orx_path_query: radius must be in [1, ORX_VIEW_MAX_RADIUS]");
-  if (n_games <= 0 || n_games > 0x7FFFFFFFLL)
-    return fail(ORX_EINVAL, "orx_path_query: bad n_games");
-  if (!st) return fail(ORX_EINVAL, "state is NULL");
-  if (!st->p_x || !st->p_y) return fail(ORX_EINVAL, "a required state pointer is NULL");
+  if ((r = check_games("orx_path_query", n_games)) ||
+      (r = check_state(cfg, st, cfg->n_layouts > 0 ? 0 : kStairs)))
+    return r;
   if (cfg->n_layouts > 0) {
     if (!st->p_layout) return fail(ORX_EINVAL, "n_layouts > 0 needs p_layout");
     if (!field) return fail(ORX_EINVAL, "orx_path_query: n_layouts > 0 needs field");
-  } else {
-    if (!st->st_x || !st->st_y) return fail(ORX_EINVAL, "a required state pointer is NULL");
+  } else if ((int64_t)cfg->width + cfg->height - 6 >= (int64_t)ORX_PATH_UNREACHABLE) {
     // the closed form's largest value, (W - 3) + (H - 3), must stay below the sentinels
-    if ((int64_t)cfg->width + cfg->height - 6 >= (int64_t)ORX_PATH_UNREACHABLE)
-      return fail(ORX_EINVAL, "orx_path_query: W + H too large for uint16 distances");
+    return fail(ORX_EINVAL, "orx_path_query: W + H too large for uint16 distances");
   }
 
   PathArgs a;
@@ -412,15 +381,10 @@ extern "C" int orx_path_query(const orx_cfg_t* cfg, const orx_state_t* st, const
     hipLaunchKernelGGL(point_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
     return orx_dev::launch_status("orx_path_query");
   }
-  a.R = radius;
-  const int V = 2 * radius + 1, VV = V * V;
-  a.inv_vv = (uint32_t)(0x100000000ULL / (uint64_t)VV) + 1u;
-  a.inv_v = (uint32_t)(0x100000000ULL / (uint64_t)V) + 1u;
-  // games per workgroup: the most (64, 32, 16) whose tile fits the budget
-  int G = 64;
-  while (G > 16 && G * VV * (int)sizeof(uint16_t) > kTileBudget) G >>= 1;
-  a.G = G;
-  const size_t lds = (size_t)G * VV * sizeof(uint16_t) + sizeof(int32_t) * G * kHdr;
+  const Window win = Window::fit(radius, sizeof(uint16_t));
+  const int G = win.G;
+  a.R = win.R, a.G = G, a.inv_vv = win.inv_vv, a.inv_v = win.inv_v;
+  const size_t lds = (size_t)G * win.VV * sizeof(uint16_t) + sizeof(int32_t) * G * kHdr;
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   hipLaunchKernelGGL(window_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, a);
   return orx_dev::launch_status("orx_path_query");

@@ -33,23 +33,15 @@
 //      aligned when the buffer does), with a byte tail for the last partial
 //      workgroup's unaligned end.
 // Plain C++ and vector stores only.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
 #include <cstdlib>
 
 #include "../../include/orx_view.h"
-
-// the host side's error path (orx_engine.hip, "Host side of the C-ABI")
-namespace orx_dev {
-int fail(int code, const char* msg);
-int launch_status(const char* what);
-}  // namespace orx_dev
+#include "orx_query.h"
 
 namespace orx_view_dev {
 
-constexpr int kBlock = 256;
-constexpr int kTileBudget = 40 * 1024;  // LDS bytes of a workgroup's tiles (cells + health)
+using namespace orx_query;
+
 constexpr int kChunk = 16;              // NPC slots staged in LDS at a time (ORX_MAX_REG_NPCS)
 
 // header fields staged per game ([kHdr][G] int32 in LDS)
@@ -72,7 +64,7 @@ struct ViewArgs {
   uint8_t* health;
   int64_t B;
   int32_t W, H, K, L, R, G, player, npc_depth, items;
-  uint32_t inv_vv, inv_v;  // 2^32 / (V * V) + 1 and 2^32 / V + 1: __umulhi(n, inv) = n / d for n < 2^16
+  uint32_t inv_vv, inv_v;  // (R, G, inv_vv, inv_v: a Window)
 };
 
 __device__ __forceinline__ uint32_t clamp_u8(int32_t v) {
@@ -82,17 +74,6 @@ __device__ __forceinline__ uint32_t clamp_u8(int32_t v) {
 // bits 0..3 of n -> the low bit of bytes 0..3
 __device__ __forceinline__ uint32_t spread4(uint32_t n) {
   return ((n & 15u) * 0x00204081u) & 0x01010101u;
-}
-
-// tile[0 .. n) (LDS, 16-byte aligned) -> out[0 .. n): 16 bytes per lane while
-// the destination is 16-byte aligned, the rest (and everything, for a
-// destination that is not) byte by byte
-__device__ __forceinline__ void stream_out(const uint8_t* tile, uint8_t* out, int n, int t) {
-  const int nvec = ((reinterpret_cast<uintptr_t>(out) & 15) == 0) ? n >> 4 : 0;
-  const uint4* src = reinterpret_cast<const uint4*>(tile);
-  uint4* dst = reinterpret_cast<uint4*>(out);
-  for (int v = t; v < nvec; v += kBlock) dst[v] = src[v];
-  for (int i = (nvec << 4) + t; i < n; i += kBlock) out[i] = tile[i];
 }
 
 // NPC slots k0 .. k0 + kChunk of the workgroup's games -> stage, one lane per
@@ -112,7 +93,8 @@ __device__ __forceinline__ void stage_npcs(const ViewArgs& a, uint32_t* stage, i
 
 __global__ __launch_bounds__(kBlock) void view_kernel(const ViewArgs a) {
   extern __shared__ uint4 smem[];
-  const int G = a.G, R = a.R, V = 2 * R + 1, VV = V * V, W = a.W, H = a.H;
+  const Window win = Window::of(a.R, a.G, a.inv_vv, a.inv_v);
+  const int G = win.G, R = win.R, V = win.V, VV = win.VV, W = a.W, H = a.H;
   const int tile_bytes = (G * VV + 15) & ~15;
   uint8_t* tile = reinterpret_cast<uint8_t*>(smem);
   uint8_t* htile = tile + tile_bytes;  // (only when a.health)
@@ -126,8 +108,7 @@ __global__ __launch_bounds__(kBlock) void view_kernel(const ViewArgs a) {
 
   // 1. everything read from HBM, coalesced over the games
   if (t < nb) {
-    const int64_t b = b0 + t;
-    const int64_t me = (int64_t)a.player * B + b, ot = (int64_t)(1 - a.player) * B + b;
+    const auto [me, ot] = player_rows(a.player, B, b0 + t);
     const int32_t d = a.p_depth[me];
     hdr[H_PX * G + t] = a.p_x[me];
     hdr[H_PY * G + t] = a.p_y[me];
@@ -137,12 +118,7 @@ __global__ __launch_bounds__(kBlock) void view_kernel(const ViewArgs a) {
     hdr[H_OHP * G + t] = (int32_t)clamp_u8(a.p_health[ot]);
     hdr[H_SX * G + t] = a.st_x[me];
     hdr[H_SY * G + t] = a.st_y[me];
-    int32_t lay = 0;
-    if (a.L > 0) {  // (clamped: the tile lookup must stay inside the bank)
-      lay = a.p_layout[me];
-      lay = lay < 0 ? 0 : lay >= a.L ? a.L - 1 : lay;
-    }
-    hdr[H_LAYOUT * G + t] = lay;
+    hdr[H_LAYOUT * G + t] = layout_of(a, me);
   }
   if (a.K > 0) stage_npcs(a, npc_stage, 0, b0, nb, t);
   if (a.items) {  // (K <= kChunk with items)
@@ -171,11 +147,8 @@ __global__ __launch_bounds__(kBlock) void view_kernel(const ViewArgs a) {
     // grid / is Wall -- and the cell code is their sum (0, 1 or 2)
     const int nvec = (nb * VV + 15) >> 4;
     for (int v = t; v < nvec; v += kBlock) {
-      const uint32_t c = (uint32_t)v << 4;
-      int g = (int)__umulhi(c, a.inv_vv);          // c / VV (exact: c < 2^16)
-      const uint32_t r = c - (uint32_t)(g * VV);
-      int j = (int)__umulhi(r, a.inv_v);           // r / V
-      int i = (int)r - j * V;
+      const Window::Cell first = win.split((uint32_t)v << 4);
+      int g = first.g, j = first.j, i = first.i;
       uint32_t inb = 0, wallb = 0;
       int filled = 0;
       while (filled < 16) {
@@ -286,22 +259,17 @@ extern "C" int orx_view(const orx_cfg_t* cfg, const orx_state_t* st, int32_t pla
                         uint8_t* cells, uint8_t* health, int64_t n_games, void* stream) {
   using namespace orx_view_dev;
   using orx_dev::fail;
-  if (const int r = orx_validate_cfg(cfg)) return r;
-  if (player != 0 && player != 1) return fail(ORX_EINVAL, "orx_view: player must be 0 or 1");
+  int r;
+  if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_view", player))) return r;
   if (radius < 1 || radius > ORX_VIEW_MAX_RADIUS)
     return fail(ORX_EINVAL, "orx_view: radius must be in [1, ORX_VIEW_MAX_RADIUS]");
   if (!cells) return fail(ORX_EINVAL, "orx_view: cells is NULL");
-  if (n_games <= 0 || n_games > 0x7FFFFFFFLL) return fail(ORX_EINVAL, "orx_view: bad n_games");
-  if (!st) return fail(ORX_EINVAL, "state is NULL");
-  if (!st->p_x || !st->p_y || !st->p_depth || !st->p_health || !st->st_x || !st->st_y)
-    return fail(ORX_EINVAL, "a required state pointer is NULL");
-  if (cfg->n_npcs > 0 && (!st->npc_pos || !st->npc_health || !st->npc_alive))
-    return fail(ORX_EINVAL, "n_npcs > 0 needs npc_pos, npc_health and npc_alive");
-  if (cfg->n_layouts > 0 && (!st->p_layout || !st->bank_tiles))
-    return fail(ORX_EINVAL, "n_layouts > 0 needs p_layout and bank_tiles");
-  const bool items = (cfg->flags & ORX_EXT_ITEMS) && cfg->n_npcs > 0;
-  if (items && (!st->item_pos || !st->item_mask))
-    return fail(ORX_EINVAL, "ORX_EXT_ITEMS needs item_pos and item_mask");
+  // (the NPCs before the bank: the order this entry point refuses in)
+  if ((r = check_games("orx_view", n_games)) ||
+      (r = check_state(cfg, st, kPlayers | kStairs | kNpcs)) ||
+      (r = check_state(cfg, st, kBank | kItems)))
+    return r;
+  const bool items = has_items(cfg);
 
   ViewArgs a;
   a.p_x = st->p_x, a.p_y = st->p_y, a.p_depth = st->p_depth, a.p_health = st->p_health;
@@ -311,24 +279,17 @@ extern "C" int orx_view(const orx_cfg_t* cfg, const orx_state_t* st, int32_t pla
   a.item_pos = st->item_pos, a.item_mask = st->item_mask;
   a.cells = cells, a.health = health;
   a.B = n_games;
-  a.W = cfg->width, a.H = cfg->height, a.K = cfg->n_npcs, a.L = cfg->n_layouts, a.R = radius;
+  a.W = cfg->width, a.H = cfg->height, a.K = cfg->n_npcs, a.L = cfg->n_layouts;
   a.player = player;
-  a.npc_depth = cfg->start_mode == ORX_START_SEPARATED ? cfg->p1_depth : 0;
+  a.npc_depth = npc_depth(cfg);
   a.items = items ? 1 : 0;
-  a.inv_vv = (uint32_t)(0x100000000ULL / (uint64_t)((2 * radius + 1) * (2 * radius + 1))) + 1u;
-  a.inv_v = (uint32_t)(0x100000000ULL / (uint64_t)(2 * radius + 1)) + 1u;
-  // games per workgroup: the most (64, 32, 16) whose tiles fit the budget
-  // (env ORX_VIEW_GAMES = 16 / 32 / 64 caps it: measurements; results do not
-  // depend on it)
-  const int VV = (2 * radius + 1) * (2 * radius + 1), nout = health ? 2 : 1;
-  int G = 64;
-  if (const char* e = getenv("ORX_VIEW_GAMES")) {
-    const int v = atoi(e);
-    if (v == 16 || v == 32) G = v;
-  }
-  while (G > 16 && ((G * VV + 15) & ~15) * nout > kTileBudget) G >>= 1;
-  a.G = G;
-  const size_t lds = (size_t)((G * VV + 15) & ~15) * nout +
+  // (env ORX_VIEW_GAMES = 16 / 32 caps the games per workgroup: measurements)
+  const char* e = getenv("ORX_VIEW_GAMES");
+  const int cap = e ? atoi(e) : 64, nout = health ? 2 : 1;
+  const Window win = Window::fit(radius, nout, cap == 16 || cap == 32 ? cap : 64);
+  const int G = win.G;
+  a.R = win.R, a.G = G, a.inv_vv = win.inv_vv, a.inv_v = win.inv_v;
+  const size_t lds = (size_t)((G * win.VV + 15) & ~15) * nout +
                      sizeof(int32_t) * G * (kHdr + (a.K > 0 ? kChunk : 0) + (items ? kChunk : 0));
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   hipLaunchKernelGGL(view_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, a);

@@ -203,6 +203,34 @@ class BatchedEngine:
                 code = fn(self._pcfg, self._pst, *args)
         _lib.check(name, code)
 
+    def _require(self, name: str) -> None:
+        if not hasattr(self.lib, name):
+            raise RuntimeError(f"liborx.so has no {name} -- rebuild it "
+                               "(python -m optimax_rogue_amd.build)")
+
+    def _outs(self, out, specs, what: str, align: int = 0, distinct=None) -> list:
+        """A query's output tensors: fresh ones for ``specs`` ((dtype, shape)
+        each), or ``out`` (a tensor or a tuple, ``what``) checked against them.
+        The kernels write these shapes blindly (with ``align``, a row per
+        vector store): a wrong buffer would be an out-of-bounds or misaligned
+        device access.  ``distinct``: the names of outputs that must differ."""
+        if out is None:
+            return [torch.empty(shape, dtype=dt, device=self.device) for dt, shape in specs]
+        outs = list(out) if isinstance(out, (tuple, list)) else [out]
+        if len(outs) != len(specs):
+            raise ValueError(f"out must be {what}")
+        aligned = f", {align}-byte aligned" if align else ""
+        for t, (dt, shape) in zip(outs, specs):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape \
+                    or not t.is_contiguous() or t.device != self.device \
+                    or (align and t.data_ptr() % align):
+                raise ValueError(f"out must hold a contiguous{aligned} {dt} {shape} tensor on "
+                                 f"{self.device}")
+        if distinct and len({t.data_ptr() for t in outs}) != len(outs):
+            raise ValueError(f"out: {', '.join(distinct[:-1])} and {distinct[-1]} must be "
+                             "different tensors")
+        return outs
+
     def rollout_launcher(self, n_ticks: int, p1: int = Policy.Random, p2: int = Policy.Random,
                          obs: Optional[torch.Tensor] = None, act: Optional[torch.Tensor] = None,
                          obs_format: int = OBS_INT32):
@@ -457,28 +485,11 @@ class BatchedEngine:
         The host reference is ``view.render_view(self.snapshot(), ...)``."""
         from .view import check_view_args
         check_view_args(player, radius)
-        if not hasattr(self.lib, "orx_view"):
-            raise RuntimeError("liborx.so has no orx_view -- rebuild it "
-                               "(python -m optimax_rogue_amd.build)")
+        self._require("orx_view")
         V = 2 * int(radius) + 1
-        shape = (self.B, V, V)
-        if out is None:
-            outs = [torch.empty(shape, dtype=torch.uint8, device=self.device)
-                    for _ in range(2 if health else 1)]
-        else:
-            outs = list(out) if isinstance(out, (tuple, list)) else [out]
-            if len(outs) != (2 if health else 1):
-                raise ValueError("out must be one tensor, or (cells, health) with health=True")
-            # the kernel writes [n_games, V, V] blindly: a wrong buffer would
-            # be an out-of-bounds device access, so it is refused here
-            for t in outs:
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 \
-                        or tuple(t.shape) != shape or not t.is_contiguous() \
-                        or t.device != self.device:
-                    raise ValueError(f"out must be a contiguous uint8 {shape} tensor on "
-                                     f"{self.device}")
-            if health and outs[0].data_ptr() == outs[1].data_ptr():
-                raise ValueError("out: cells and health must be different tensors")
+        outs = self._outs(out, [(torch.uint8, (self.B, V, V))] * (2 if health else 1),
+                          "one tensor, or (cells, health) with health=True",
+                          distinct=("cells", "health"))
         self._call("orx_view", int(player), int(radius), _ptr(outs[0]),
                    _ptr(outs[1]) if health else None, self.B, self._stream())
         return (outs[0], outs[1]) if health else outs[0]
@@ -492,9 +503,7 @@ class BatchedEngine:
         if self.bank is None:
             return None
         if self._stair_field is None:
-            if not hasattr(self.lib, "orx_path_field"):
-                raise RuntimeError("liborx.so has no orx_path_field -- rebuild it "
-                                   "(python -m optimax_rogue_amd.build)")
+            self._require("orx_path_field")
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("the staircase field is computed at the first path() call: "
                                    "call path() (or read stair_field) once before capturing")
@@ -525,26 +534,12 @@ class BatchedEngine:
         ``path.query(self.snapshot(), ...)``."""
         from .path import check_path_args
         check_path_args(player, radius, self.cfg)
-        if not hasattr(self.lib, "orx_path_query"):
-            raise RuntimeError("liborx.so has no orx_path_query -- rebuild it "
-                               "(python -m optimax_rogue_amd.build)")
+        self._require("orx_path_query")
         specs = [(torch.int32, (self.B,)), (torch.int8, (self.B,))]
         if radius is not None:
             V = 2 * int(radius) + 1
             specs.append((torch.uint16, (self.B, V, V)))
-        if out is None:
-            outs = [torch.empty(shape, dtype=dt, device=self.device) for dt, shape in specs]
-        else:
-            outs = list(out) if isinstance(out, (tuple, list)) else [out]
-            if len(outs) != len(specs):
-                raise ValueError("out must be (dist, move), or (dist, move, window) with a radius")
-            # the kernel writes these shapes blindly: a wrong buffer would be
-            # an out-of-bounds device access, so it is refused here
-            for t, (dt, shape) in zip(outs, specs):
-                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape \
-                        or not t.is_contiguous() or t.device != self.device:
-                    raise ValueError(f"out must hold a contiguous {dt} {shape} tensor on "
-                                     f"{self.device}")
+        outs = self._outs(out, specs, "(dist, move), or (dist, move, window) with a radius")
         field = self.stair_field
         self._call("orx_path_query", _ptr(field), int(player), int(radius or 0), _ptr(outs[0]),
                    _ptr(outs[1]), _ptr(outs[2]) if radius is not None else None, self.B,
@@ -567,28 +562,11 @@ class BatchedEngine:
         reference is ``moves.outcomes(cfg, self.snapshot(), player)``."""
         from .moves import MOVES_COLS, check_moves_args
         check_moves_args(player)
-        if not hasattr(self.lib, "orx_moves"):
-            raise RuntimeError("liborx.so has no orx_moves -- rebuild it "
-                               "(python -m optimax_rogue_amd.build)")
+        self._require("orx_moves")
         shape = (self.B, MOVES_COLS)
-        specs = [(torch.uint8, shape), (torch.int16, shape), (torch.int16, shape)]
-        if out is None:
-            outs = [torch.empty(shape, dtype=dt, device=self.device) for dt, shape in specs]
-        else:
-            outs = list(out) if isinstance(out, (tuple, list)) else [out]
-            if len(outs) != len(specs):
-                raise ValueError("out must be (kind, target, amount)")
-            # the kernel writes these shapes blindly, a row per vector store: a
-            # wrong buffer would be an out-of-bounds (or misaligned) device
-            # access, so it is refused here
-            for t, (dt, shape) in zip(outs, specs):
-                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape \
-                        or not t.is_contiguous() or t.device != self.device \
-                        or t.data_ptr() % 16:
-                    raise ValueError(f"out must hold a contiguous, 16-byte aligned {dt} {shape} "
-                                     f"tensor on {self.device}")
-            if len({t.data_ptr() for t in outs}) != len(outs):
-                raise ValueError("out: kind, target and amount must be different tensors")
+        outs = self._outs(out, [(torch.uint8, shape), (torch.int16, shape), (torch.int16, shape)],
+                          "(kind, target, amount)", align=16,
+                          distinct=("kind", "target", "amount"))
         self._call("orx_moves", int(player), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), self.B,
                    self._stream())
         return tuple(outs)
@@ -599,9 +577,7 @@ class BatchedEngine:
         the stores)."""
         from .moves import MOVES_COLS, check_moves_args
         check_moves_args(player)
-        if not hasattr(self.lib, "orx_moves"):
-            raise RuntimeError("liborx.so has no orx_moves -- rebuild it "
-                               "(python -m optimax_rogue_amd.build)")
+        self._require("orx_moves")
         kind = torch.empty((self.B, MOVES_COLS), dtype=torch.uint8, device=self.device)
         self._call("orx_moves", int(player), _ptr(kind), None, None, self.B, self._stream())
         return kind

@@ -31,8 +31,8 @@ from __future__ import annotations
 import numpy as np
 
 from .enums import (EXT_CHARACTER, EXT_HEAL, EXT_ITEMS, EXT_MANA, EXT_README_COMBAT, MOVE_HEAL,
-                    Move, RPG_FIELDS, Tile, npc_alive_bits)
-from .view import npc_depth
+                    Move, RPG_FIELDS, Tile)
+from .query import MOVE_DELTAS, check_player, i64, item_rows, npc_depth, npc_rows, tile_at
 
 # include/orx_moves.h ORX_MOVES_COLS, ORX_OUT_*
 MOVES_COLS = 8
@@ -51,10 +51,6 @@ OUT_COOLDOWN = 32
 
 OUT_NAMES = ("NONE", "REST", "BLOCKED", "STEP", "DESCEND", "ATTACK_NPC", "ATTACK_PLAYER", "HEAL")
 
-# calculate_pos (updater.py:340-351)
-MOVE_DELTAS = ((int(Move.Up), 0, -1), (int(Move.Right), 1, 0), (int(Move.Down), 0, 1),
-               (int(Move.Left), -1, 0))
-
 
 def move_count(cfg) -> int:
     """M: the moves of a configuration, 5, or 6 with EXT_HEAL."""
@@ -64,8 +60,7 @@ def move_count(cfg) -> int:
 def check_moves_args(player: int) -> None:
     """ValueError for a player other than 0 / 1 (what orx_moves refuses with
     ORX_EINVAL)."""
-    if player not in (0, 1):
-        raise ValueError(f"player must be 0 or 1, got {player!r}")
+    check_player(player)
 
 
 def outcomes(cfg, state: dict, player: int, layouts=None):
@@ -75,14 +70,12 @@ def outcomes(cfg, state: dict, player: int, layouts=None):
     DungeonBank; ``cfg.layouts`` when omitted; the state then has
     ``p_layout``)."""
     check_moves_args(player)
-    W, H, K = int(cfg.width), int(cfg.height), int(cfg.n_npcs)
-    flags = int(cfg.flags)
+    K, flags = int(cfg.n_npcs), int(cfg.flags)
     if layouts is None:
         layouts = getattr(cfg, "layouts", None)
     if layouts is not None:
         layouts = np.asarray(getattr(layouts, "layouts", layouts))
     p, q = int(player), 1 - int(player)
-    i64 = lambda a: np.asarray(a).astype(np.int64)
     x, y, d, hp = (i64(state[f][p]) for f in ("p_x", "p_y", "p_depth", "p_health"))
     ox, oy, od, ohp = (i64(state[f][q]) for f in ("p_x", "p_y", "p_depth", "p_health"))
     B = len(x)
@@ -106,35 +99,21 @@ def outcomes(cfg, state: dict, player: int, layouts=None):
 
     on_npc_depth = d == npc_depth(cfg)
     if K:
-        alive = npc_alive_bits(np.asarray(state["npc_alive"]).astype(np.uint32), K)
-        npos = np.asarray(state["npc_pos"]).astype(np.uint16).astype(np.int64)[:K]
-        nhp = i64(np.asarray(state["npc_health"]).astype(np.int8))[:K]
+        alive, nx, ny, nhp = npc_rows(state, K)
     items = bool(K and flags & EXT_ITEMS and "item_mask" in state)
     if items:
-        imask = np.asarray(state["item_mask"]).astype(np.uint32).astype(np.int64)
-        ipos = np.asarray(state["item_pos"]).astype(np.uint16).astype(np.int64)
+        on_floor, ix, iy, _ = item_rows(state, K)
 
     games = np.arange(B)
     for m, dx, dy in MOVE_DELTAS:
         tx, ty = x + dx, y + dy
-        inside = (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-        cx, cy = np.clip(tx, 0, W - 1), np.clip(ty, 0, H - 1)
-        if layouts is None:
-            # EmptyDungeonGenerator (worldgen.py:33-43): border Wall, one staircase
-            tile = np.where((tx == 0) | (tx == W - 1) | (ty == 0) | (ty == H - 1), int(Tile.Wall),
-                            int(Tile.Ground))
-            sx, sy = i64(state["st_x"][p]), i64(state["st_y"][p])
-            tile = np.where((tile != int(Tile.Wall)) & (tx == sx) & (ty == sy),
-                            int(Tile.StaircaseDown), tile)
-        else:
-            lay = np.clip(i64(state["p_layout"][p]), 0, len(layouts) - 1)
-            tile = layouts[lay, cx, cy].astype(np.int64) & 3
+        inside, tile = tile_at(cfg, state, p, tx, ty, layouts)
         blocked = ~inside | (tile == int(Tile.Wall))                   # Dungeon.is_blocked
         at_player = ~blocked & (od == d) & (tx == ox) & (ty == oy)
         # the first live NPC on the target, in slot order (pos_lookup)
         slot = np.full(B, -1, np.int64)
         for k in range(K - 1, -1, -1):
-            hit = on_npc_depth & alive[k] & ((npos[k] & 0xFF) == tx) & ((npos[k] >> 8) == ty)
+            hit = on_npc_depth & alive[k] & (nx[k] == tx) & (ny[k] == ty)
             slot[hit] = k
         at_npc = ~blocked & ~at_player & (slot >= 0)
         free = ~blocked & ~at_player & ~at_npc
@@ -162,7 +141,7 @@ def outcomes(cfg, state: dict, player: int, layouts=None):
         if items:
             lies = np.zeros(B, bool)
             for k in range(K):
-                lies |= (((imask[0] >> k) & 1) == 1) & ((ipos[k] & 0xFF) == tx) & ((ipos[k] >> 8) == ty)
+                lies |= on_floor[k] & (ix[k] == tx) & (iy[k] == ty)
             k_m[step & on_npc_depth & lies & (held < int(cfg.item_slots))] |= OUT_ITEM
         kind[:, m] = k_m
 

@@ -25,16 +25,12 @@ from __future__ import annotations
 import numpy as np
 
 from .enums import Move, Tile
-from .view import VIEW_MAX_RADIUS
+from .query import (MOVE_DELTAS, bank_at, check_player, check_radius, i64, inside_grid, tile_at,
+                    window_cells)
 
 # include/orx_path.h ORX_PATH_*
 PATH_WALL = 0xFFFF
 PATH_UNREACHABLE = 0xFFFE
-
-# calculate_pos (updater.py:340-351): Up is y - 1, Right x + 1, Down y + 1,
-# Left x - 1; the order in which ``move`` tries them (the Move codes 1..4)
-MOVE_DELTAS = ((int(Move.Up), 0, -1), (int(Move.Right), 1, 0), (int(Move.Down), 0, 1),
-               (int(Move.Left), -1, 0))
 
 
 def check_path_args(player: int, radius=None, cfg=None) -> None:
@@ -42,12 +38,9 @@ def check_path_args(player: int, radius=None, cfg=None) -> None:
     outside 1..VIEW_MAX_RADIUS, or an EmptyDungeonGenerator grid whose largest
     distance (W - 3) + (H - 3) would reach the sentinels (what orx_path_query
     refuses with ORX_EINVAL)."""
-    if player not in (0, 1):
-        raise ValueError(f"player must be 0 or 1, got {player!r}")
-    if radius is not None and (not isinstance(radius, (int, np.integer))
-                               or not 1 <= radius <= VIEW_MAX_RADIUS):
-        raise ValueError(f"radius must be None or an integer in [1, {VIEW_MAX_RADIUS}], "
-                         f"got {radius!r}")
+    check_player(player)
+    if radius is not None:
+        check_radius(radius)
     if cfg is not None and getattr(cfg, "layouts", None) is None \
             and int(cfg.width) + int(cfg.height) - 6 >= PATH_UNREACHABLE:
         raise ValueError("width + height too large for uint16 distances")
@@ -128,28 +121,24 @@ def query(snap: dict, cfg, player: int, radius=None, bank=None):
     a bank (made from ``cfg.layouts`` when omitted), else ``closed_form`` with
     the staircase (st_x, st_y)[player] of the player's depth."""
     check_path_args(player, radius, cfg)
-    W, H = int(cfg.width), int(cfg.height)
     if bank is None and getattr(cfg, "layouts", None) is not None:
         from .dungeons import DungeonBank
         bank = DungeonBank(cfg.layouts)
     p = int(player)
-    i64 = lambda a: np.asarray(a).astype(np.int64)
     px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
     if bank is None:
         sx, sy = i64(snap["st_x"][p]), i64(snap["st_y"][p])
     else:
         field = bank.stair_field()
-        lay = np.clip(i64(snap["p_layout"][p]), 0, len(bank) - 1)
 
     def value(x, y):
         """The values of cells (x, y), arrays of shape [B, ...]."""
-        inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
-        g = (slice(None),) + (None,) * (x.ndim - 1)
         if bank is None:
-            border = (x == 0) | (x == W - 1) | (y == 0) | (y == H - 1)
-            v = np.where(border, PATH_WALL, np.abs(x - sx[g]) + np.abs(y - sy[g]))
+            g = (slice(None),) + (None,) * (x.ndim - 1)
+            inside, tile = tile_at(cfg, snap, p, x, y)
+            v = np.where(tile == int(Tile.Wall), PATH_WALL, np.abs(x - sx[g]) + np.abs(y - sy[g]))
         else:
-            v = field[lay[g], np.clip(x, 0, W - 1), np.clip(y, 0, H - 1)].astype(np.int64)
+            inside, v = inside_grid(cfg, x, y), bank_at(field, snap, p, x, y).astype(np.int64)
         return np.where(inside, v, PATH_WALL)
 
     own = value(px, py)
@@ -157,10 +146,4 @@ def query(snap: dict, cfg, player: int, radius=None, bank=None):
     move = move_toward(own, *(value(px + dx, py + dy) for _, dx, dy in MOVE_DELTAS))
     if radius is None:
         return dist, move
-    R = int(radius)
-    V = 2 * R + 1
-    off = np.arange(V) - R
-    B = len(px)
-    x = np.broadcast_to(px[:, None, None] + off[None, None, :], (B, V, V))   # columns are x
-    y = np.broadcast_to(py[:, None, None] + off[None, :, None], (B, V, V))   # rows are y
-    return dist, move, value(x, y).astype(np.uint16)
+    return dist, move, value(*window_cells(px, py, int(radius))).astype(np.uint16)

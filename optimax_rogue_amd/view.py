@@ -25,10 +25,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from .enums import EXT_ITEMS, StartMode, Tile, npc_alive_bits
+from .enums import EXT_ITEMS, Tile
+from .query import (MAX_RADIUS, check_player, check_radius, i64, item_rows, npc_depth,  # noqa: F401
+                    npc_rows, tile_at, window_cells)
 
 # include/orx_view.h ORX_VIEW_*
-VIEW_MAX_RADIUS = 15
+VIEW_MAX_RADIUS = MAX_RADIUS
 VIEW_TILE_MASK = 3
 VIEW_OUTSIDE = 0
 VIEW_PLAYER = 4
@@ -40,16 +42,8 @@ VIEW_ITEM_KIND = 32
 def check_view_args(player: int, radius: int) -> None:
     """ValueError for a player other than 0 / 1 or a radius outside
     1..VIEW_MAX_RADIUS (what orx_view refuses with ORX_EINVAL)."""
-    if player not in (0, 1):
-        raise ValueError(f"player must be 0 or 1, got {player!r}")
-    if not isinstance(radius, (int, np.integer)) or not 1 <= radius <= VIEW_MAX_RADIUS:
-        raise ValueError(f"radius must be an integer in [1, {VIEW_MAX_RADIUS}], got {radius!r}")
-
-
-def npc_depth(cfg) -> int:
-    """The depth the NPCs (and the items they drop) are on: player 1's start
-    depth."""
-    return int(cfg.p1_depth) if int(cfg.start_mode) == StartMode.Separated else 0
+    check_player(player)
+    check_radius(radius)
 
 
 def render_view(snap: dict, cfg, player: int, radius: int, bank=None, health: bool = False):
@@ -67,24 +61,11 @@ def render_view(snap: dict, cfg, player: int, radius: int, bank=None, health: bo
         from .dungeons import DungeonBank
         bank = DungeonBank(cfg.layouts)
     p, q = int(player), 1 - int(player)
-    i64 = lambda a: np.asarray(a).astype(np.int64)
     px, py, d = i64(snap["p_x"][p]), i64(snap["p_y"][p]), i64(snap["p_depth"][p])
     B = len(px)
-    off = np.arange(V) - R
-    x = np.broadcast_to(px[:, None, None] + off[None, None, :], (B, V, V))   # columns are x
-    y = np.broadcast_to(py[:, None, None] + off[None, :, None], (B, V, V))   # rows are y
-    inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
-    if bank is None:
-        # EmptyDungeonGenerator (worldgen.py:33-43): border Wall, one staircase
-        tile = np.where((x == 0) | (x == W - 1) | (y == 0) | (y == H - 1), int(Tile.Wall),
-                        int(Tile.Ground))
-        sx, sy = i64(snap["st_x"][p]), i64(snap["st_y"][p])
-        tile = np.where((x == sx[:, None, None]) & (y == sy[:, None, None]),
-                        int(Tile.StaircaseDown), tile)
-    else:
-        lay = np.clip(i64(snap["p_layout"][p]), 0, len(bank) - 1)
-        tile = bank.layouts[lay[:, None, None], np.clip(x, 0, W - 1), np.clip(y, 0, H - 1)]
-        tile = tile.astype(np.int64) & VIEW_TILE_MASK
+    x, y = window_cells(px, py, R)
+    inside, tile = tile_at(cfg, snap, p, x, y, None if bank is None else bank.layouts,
+                           stair_on_border=True)
     cells = np.where(inside, tile, VIEW_OUTSIDE).astype(np.uint8)
     hp = np.zeros((B, V, V), np.uint8)
 
@@ -101,17 +82,13 @@ def render_view(snap: dict, cfg, player: int, radius: int, bank=None, health: bo
 
     on_npc_depth = d == npc_depth(cfg)
     if K and int(cfg.flags) & EXT_ITEMS and "item_mask" in snap:
-        mask = np.asarray(snap["item_mask"]).astype(np.uint32).astype(np.int64)
-        pos = np.asarray(snap["item_pos"]).astype(np.uint16).astype(np.int64)
+        on, ix, iy, kind = item_rows(snap, K)
         for k in range(K):
-            bits = VIEW_ITEM + VIEW_ITEM_KIND * ((mask[1] >> k) & 1)
-            mark(on_npc_depth & (((mask[0] >> k) & 1) == 1), pos[k] & 0xFF, pos[k] >> 8, bits)
+            mark(on_npc_depth & on[k], ix[k], iy[k], VIEW_ITEM + VIEW_ITEM_KIND * kind[k])
     if K:
-        alive = npc_alive_bits(np.asarray(snap["npc_alive"]).astype(np.uint32), K)
-        pos = np.asarray(snap["npc_pos"]).astype(np.uint16).astype(np.int64)
-        nhp = i64(np.asarray(snap["npc_health"]).astype(np.int8))
+        alive, nx, ny, nhp = npc_rows(snap, K)
         for k in range(K):
-            mark(on_npc_depth & alive[k], pos[k] & 0xFF, pos[k] >> 8, VIEW_NPC, nhp[k])
+            mark(on_npc_depth & alive[k], nx[k], ny[k], VIEW_NPC, nhp[k])
     # the other player last: its health takes the health byte
     mark(i64(snap["p_depth"][q]) == d, i64(snap["p_x"][q]), i64(snap["p_y"][q]), VIEW_PLAYER,
          i64(snap["p_health"][q]))

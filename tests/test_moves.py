@@ -112,8 +112,8 @@ def test_header_constants_are_the_modules():
 
 def test_moves_symbols_and_build_id(engine_lib):
     """The library exports the header's entry points, and its moves id is the
-    hash of the tree's orx_moves.hip and orx_moves.h (a stale library is
-    rebuilt: build.build compares all three ids)."""
+    hash of the tree's orx_moves.hip, orx_moves.h and the queries' shared
+    header (a stale library is rebuilt: build.build compares all three ids)."""
     import hashlib
     import subprocess
     from optimax_rogue_amd import _lib, build
@@ -123,12 +123,12 @@ def test_moves_symbols_and_build_id(engine_lib):
     for name in _lib.MOVES_EXPORTS:
         assert hasattr(engine_lib, name)
     h = hashlib.sha256()
-    for p in (build.MOVES_SRC, build.MOVES_HDR):
+    for p in (build.MOVES_SRC, build.MOVES_HDR, build.QUERY_HDR):
         with open(p, "rb") as f:
             h.update(f.read())
     assert build.moves_id() == h.hexdigest()[:16] == _lib.moves_build_id()
-    assert build.built_moves_id(_lib.LIB_PATH) == build.moves_id()
-    assert build.built_ids(_lib.LIB_PATH) == (build.source_id(), build.path_id())
+    assert build.built_ids(_lib.LIB_PATH) == {"engine": build.source_id(), "path": build.path_id(),
+                                              "moves": build.moves_id()}
     assert os.path.basename(build.MOVES_SRC) == "orx_moves.hip"
     assert os.path.basename(build.MOVES_HDR) == "orx_moves.h"
 

@@ -204,8 +204,8 @@ def test_header_constants_are_the_modules():
 
 def test_path_symbols_and_build_id(engine_lib):
     """The library exports the header's entry points, and its path id is the
-    hash of the tree's orx_path.hip and orx_path.h (a stale library is
-    rebuilt: build.build compares both ids)."""
+    hash of the tree's orx_path.hip, orx_path.h and the queries' shared header
+    (a stale library is rebuilt: build.build compares all ids)."""
     import hashlib
     import subprocess
     from optimax_rogue_amd import _lib, build
@@ -215,11 +215,12 @@ def test_path_symbols_and_build_id(engine_lib):
     for name in _lib.PATH_EXPORTS:
         assert hasattr(engine_lib, name)
     h = hashlib.sha256()
-    for p in (build.PATH_SRC, build.PATH_HDR):
+    for p in (build.PATH_SRC, build.PATH_HDR, build.QUERY_HDR):
         with open(p, "rb") as f:
             h.update(f.read())
     assert build.path_id() == h.hexdigest()[:16] == _lib.path_build_id()
-    assert build.built_ids(_lib.LIB_PATH) == (build.source_id(), build.path_id())
+    assert build.built_ids(_lib.LIB_PATH) == {"engine": build.source_id(), "path": build.path_id(),
+                                              "moves": build.moves_id()}
     assert os.path.basename(build.PATH_SRC) == "orx_path.hip"
     assert os.path.basename(build.PATH_HDR) == "orx_path.h"
 
