@@ -358,8 +358,9 @@ typedef struct orx_state {
 int orx_abi_version(void);
 
 /* Source hash the library was built from: the first 16 hex digits of the
- * SHA-256 of orx_engine.hip followed by include/orx.h, orx_view.hip and
- * include/orx_view.h (build.py), so a test can prove the loaded library is
+ * SHA-256 of orx_engine.hip followed by include/orx.h, orx_view.hip,
+ * include/orx_view.h, csrc/orx_query.h and csrc/orx_plan.h
+ * (build.PARTS["engine"].files), so a test can prove the loaded library is
  * the tree's own kernels ("unknown" for a build made outside build.py).  No
  * reference counterpart. */
 const char* orx_build_id(void);
@@ -385,8 +386,11 @@ int orx_rollout_lanes(int64_t n_games);
  * the threads per workgroup (256; 512 for a paired bank above half the LDS:
  * one workgroup per CU then holds two waves per SIMD) and the dynamic LDS
  * bytes per workgroup (a bank's tiles, dense NPCs' occupancy bitmaps);
- * concurrency as in orx_rollout_concurrent (1 for orx_rollout).  Results
- * never depend on it.  No reference counterpart. */
+ * concurrency as in orx_rollout_concurrent (1 for orx_rollout).  It is the
+ * launch's own plan (csrc/orx_plan.h) for int32 rows (the query takes no row
+ * format): with ORX_OBS_COMPACT rows a dungeon bank, dense NPCs or the
+ * character mechanics take the generic one-lane form instead.  Results never
+ * depend on it.  No reference counterpart. */
 typedef struct orx_rollout_shape {
   int32_t games_per_wave;
   int32_t lanes_per_game;

@@ -39,6 +39,7 @@ PATH_HDR = os.path.join(ROOT, "include", "orx_path.h")
 MOVES_SRC = os.path.join(PKG_DIR, "csrc", "orx_moves.hip")
 MOVES_HDR = os.path.join(ROOT, "include", "orx_moves.h")
 QUERY_HDR = os.path.join(PKG_DIR, "csrc", "orx_query.h")
+PLAN_HDR = os.path.join(PKG_DIR, "csrc", "orx_plan.h")   # the engine's launch plan (host side)
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -67,8 +68,8 @@ VARIANTS = {
 # (in this order), the sources compiled.  Ids, flags and compile list come from here.
 Part = namedtuple("Part", "symbol macro files sources")
 PARTS = {
-    "engine": Part("orx_build_id", "ORX_BUILD_ID", (SRC, HDR, VIEW_SRC, VIEW_HDR, QUERY_HDR),
-                   (SRC, VIEW_SRC)),
+    "engine": Part("orx_build_id", "ORX_BUILD_ID", (SRC, HDR, VIEW_SRC, VIEW_HDR, QUERY_HDR,
+                                                     PLAN_HDR), (SRC, VIEW_SRC)),
     "path": Part("orx_path_build_id", "ORX_PATH_BUILD_ID", (PATH_SRC, PATH_HDR, QUERY_HDR),
                  (PATH_SRC,)),
     "moves": Part("orx_moves_build_id", "ORX_MOVES_BUILD_ID", (MOVES_SRC, MOVES_HDR, QUERY_HDR),

@@ -51,6 +51,7 @@
 #include <cstring>
 
 #include "../../include/orx.h"
+#include "orx_plan.h"  // the launch plan (host side) and the constants it shares with the kernels
 
 // Split build (optimax_rogue_amd/build.py): this file is compiled ORX_NPARTS
 // times in parallel.  Part 0 holds the host side (the C-ABI) and declares
@@ -132,7 +133,7 @@ constexpr int kRolloutBlock = ORX_ROLLOUT_BLOCK;  // rollout_kernel workgroup si
 // Games per rollout wave ("lanes", a power of two 1..64) is a launch
 // argument: below 64 the wave's upper lanes idle so that a small batch still
 // puts a wave on every SIMD (orx_rollout picks it from the batch and the CU
-// count, rollout_lanes()).
+// count, orx_plan.h).
 
 #ifndef ORX_XCD_REMAP
 #define ORX_XCD_REMAP 1
@@ -345,9 +346,7 @@ struct Cfg {  // device copy of orx_cfg_t plus derived constants (all wave-unifo
 // then reads LDS instead of waiting out an L2 round trip -- at one wave per
 // SIMD nothing hides that latency).  Above kMaxLdsTiles (the default
 // per-workgroup limit) the launch raises the kernel's limit first.
-extern __shared__ uint8_t orx_lds_tiles[];
-inline constexpr uint32_t kMaxLdsTiles = 64 * 1024;
-inline constexpr uint32_t kMaxLdsBlock = 160 * 1024;  // LDS per CU (one workgroup may take it all)
+extern __shared__ uint8_t orx_lds_tiles[];  // (kMaxLdsTiles, kMaxLdsBlock: orx_plan.h)
 
 struct Deltas {  // counter / return increments, flushed once per launch
   int32_t combat, descend, dungeon, npc_death, ret, eps;
@@ -551,7 +550,7 @@ struct Npcs {
 // alive bits as rows of 32 (npc_alive [ceil(K/32)][B]).  A target test is one
 // byte load instead of a register scan; it is the form for NPC counts that
 // no register file holds (GameState.entities is unbounded, state.py:25-34).
-constexpr int kDense = 256;
+// Its NCAP is kDense (orx_plan.h).
 
 // The rollout also stages each game's occupancy as a bitmap in LDS (one bit
 // per cell, 512 B per 64x64 game), so the tick's two target tests read LDS:
@@ -5787,11 +5786,6 @@ int check_cfg(const orx_cfg_t* c) {
   return ORX_OK;
 }
 
-// The moving-NPC kernels serve this configuration (NPCs that move)
-inline bool moving_npcs(const orx_cfg_t* c) {
-  return c->npc_policy != ORX_NPC_STAY && c->n_npcs > 0;
-}
-
 int check_state(const orx_cfg_t* c, const orx_state_t* s, bool full) {
   if (!s) return fail(ORX_EINVAL, "state is NULL");
   if (!s->p_x || !s->p_y || !s->p_depth || !s->p_health || !s->st_x || !s->st_y || !s->tick ||
@@ -5852,10 +5846,6 @@ int launch_status(const char* what) {
   return ORX_OK;
 }
 
-constexpr int kBlock = 256;
-
-inline dim3 grid_for(int64_t B) { return dim3((unsigned)((B + kBlock - 1) / kBlock)); }
-
 inline Key make_key(uint64_t seed) { return Key{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
 
 int check_sizes(int64_t B, int64_t off) {
@@ -5866,25 +5856,12 @@ int check_sizes(int64_t B, int64_t off) {
   return ORX_OK;
 }
 
-// NPC slot capacity of the kernel instance for K NPCs.
-inline int ncap_for(int K) {
-  return K == 0 ? 0 : K <= 8 ? 8 : K <= ORX_MAX_REG_NPCS ? 16 : kDense;
-}
-
-// Games per rollout wave.  A rollout lane runs its game's whole tick stream,
-// so a wave's time is set by its instruction stream, not by how many of its
-// lanes are busy: a batch too small to put a wave on every SIMD (4 per CU) is
-// spread over more, narrower waves, which also take the rare block on fewer
-// ticks (C5 at 16,384 games: 232 us per 128-tick launch at 64 games per wave,
-// 158 at 16).  Not below 16: narrower waves share each 128-B trajectory line
-// among four or more waves, and launches took twice as long (C2 at 4,096
-// games: 77 us at 16, 155 at 8).  Two half-full waves per SIMD lose to one
-// full one (C3: 101 us at 64, 130 at 32), so the rule is "at most one wave per
-// SIMD until the wave is full".  The environment variable ORX_ROLLOUT_LANES
-// (1..64, a power of two) overrides it for measurements.
+// The launch plan's Device: the current device's SIMDs (4 per CU) and the
+// dynamic LDS one workgroup may declare with the opt-in limit raise (the
+// opt-in attribute, else the default per-block one), read once per device
 constexpr int kMaxDevices = 64;
-constexpr uint32_t kMinLanes = 16;
 std::atomic<int> g_cu_count[kMaxDevices];
+std::atomic<int> g_lds_block[kMaxDevices];
 
 int device_simds() {
   int dev = 0;
@@ -5898,11 +5875,6 @@ int device_simds() {
   }
   return 4 * n;
 }
-
-// Dynamic LDS one workgroup may declare on the current device with the
-// opt-in limit raise (160 KiB on gfx950): the opt-in attribute, else the
-// default per-block one, else kMaxLdsBlock; read once per device.
-std::atomic<int> g_lds_block[kMaxDevices];
 
 uint32_t device_lds_per_block() {
   int dev = 0;
@@ -5920,158 +5892,34 @@ uint32_t device_lds_per_block() {
   return (uint32_t)n;
 }
 
-bool paired_enabled() {  // read per launch (ORX_ROLLOUT_PAIRED=0: the one-lane form)
-  const char* e = getenv("ORX_ROLLOUT_PAIRED");
-  return !(e && e[0] == '0');
+inline Device device() { return Device{device_simds(), device_lds_per_block()}; }
+
+// Raises `kernel`'s dynamic-LDS limit to the plan's bytes where they exceed
+// the default 64 KiB; false when the runtime refuses, and the caller plans
+// again without a raise.
+template <class... P>
+bool raise_lds(void (*kernel)(P...), const Plan& p) {
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  if (p.lds_bytes <= kMaxLdsTiles ||
+      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes) ==
+          hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  return false;
 }
 
-int lanes_override() {  // read per launch, so a sweep can change it in-process
-  const char* e = getenv("ORX_ROLLOUT_LANES");
-  const int x = e ? atoi(e) : 0;
-  return (x >= 1 && x <= 64 && (x & (x - 1)) == 0) ? x : 0;
+// Launches `kernel` in the plan's shape -- or, given a count, one thread per
+// game in workgroups of kBlock -- and reports the launch as `what`'s.
+template <class... P, class... A>
+int launch(const char* what, void (*kernel)(P...), const Plan& p, hipStream_t s, const A&... args) {
+  hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(p.threads), p.lds_bytes, s, args...);
+  return launch_status(what);
 }
 
-// Games per wave of mov_rollout_kernel: 64 (its tick is issue-bound, so
-// fewer games per wave only add waves: 32 / 16 / 8 measured equal or slower,
-// profiles/r06_v4/ab_mov_lanes_regs.jsonl); env ORX_MOV_LANES = 1..64, a
-// power of two, overrides, for measurements and tests
-uint32_t mov_lanes() {
-  const char* e = getenv("ORX_MOV_LANES");
-  const int x = e ? atoi(e) : 0;
-  return (x >= 1 && x <= 64 && (x & (x - 1)) == 0) ? (uint32_t)x : 64u;
-}
-
-// Threads per rollout workgroup: kRolloutBlock (env ORX_ROLLOUT_THREADS = 64
-// / 128 / 256 overrides, for measurements).
-uint32_t rollout_threads(uint32_t B, uint32_t lanes) {
-  const char* e = getenv("ORX_ROLLOUT_THREADS");
-  const int x = e ? atoi(e) : 0;
-  if (x == 64 || x == 128 || x == 256) return (uint32_t)x;
-  (void)B; (void)lanes;  // single-wave workgroups for small batches measured within
-                         // +-3% (profiles/r02_v6/threads_ab.jsonl): not the default
-  return (uint32_t)kRolloutBlock;
-}
-
-uint32_t rollout_lanes(uint32_t B) {
-  if (const int o = lanes_override()) return (uint32_t)o;
-  const uint64_t simds = (uint64_t)device_simds();
-  uint32_t L = 64;
-  while (L > kMinLanes && (uint64_t)B < simds * L) L >>= 1;
-  return L;
-}
-
-// The policy mode (rollout_kernel's PM) of an orx_rollout launch: the
-// buffer-addressed trajectory forms need both buffers and one tick's obs rows
-// below 2 GiB.
-int rollout_pm(const orx_cfg_t* cfg, int32_t p1, int32_t p2, uint32_t B, bool traj) {
-  const bool traj_fast = traj && (uint64_t)B * ORX_OBS_FIELDS * 4u < (1ull << 31);
-  const bool both_random = p1 == ORX_POLICY_RANDOM && p2 == ORX_POLICY_RANDOM;
-  return !traj_fast ? 0
-         : (cfg->flags == 0 && both_random) ? 1
-         : ((cfg->flags & ~ORX_EXT_SEPARATION_DAMAGE) == 0 && p1 == ORX_POLICY_STAIRCASE &&
-            p2 == ORX_POLICY_STAIRCASE) ? 2
-         : ((cfg->flags | ORX_EXT_HEAL) == ORX_EXT_RPG && both_random &&
-            ncap_for(cfg->n_npcs) != kDense) ? 3   // (no dense-NPC instance of PM 3)
-         // one RandomBot against one StaircaseBot: paired forms only (PM 4 /
-         // 5; a launch that does not pair takes the generic form)
-         : (cfg->flags == 0 && p1 == ORX_POLICY_RANDOM && p2 == ORX_POLICY_STAIRCASE) ? 4
-         : (cfg->flags == 0 && p1 == ORX_POLICY_STAIRCASE && p2 == ORX_POLICY_RANDOM) ? 5
-         : 0;
-}
-
-// A bank's tiles staged in LDS by the rollout kernels: up to the device's
-// per-workgroup limit (160 KiB on gfx950; above the default 64 KiB the launch
-// raises the kernel's limit, raise_lds).  Env ORX_NO_LDS_TILES: never, for
-// measurements.
-bool bank_in_lds(const orx_cfg_t* cfg) {
-  const uint64_t tiles = (uint64_t)cfg->n_layouts * (uint64_t)(cfg->width * cfg->height);
-  return tiles && tiles <= device_lds_per_block() && !getenv("ORX_NO_LDS_TILES");
-}
-
-// Raises kernel `fn`'s dynamic-LDS limit to `bytes` when they exceed the
-// default 64 KiB; false when the device or the runtime refuses (env
-// ORX_REFUSE_LDS_RAISE=1 simulates a refusal, for tests), so the caller
-// launches a form that does not need them.
-bool raise_lds(const void* fn, uint32_t bytes) {
-  if (bytes <= kMaxLdsTiles) return true;
-  if (bytes > device_lds_per_block()) return false;
-  const char* e = getenv("ORX_REFUSE_LDS_RAISE");
-  if (e && e[0] == '1') return false;
-  if (!fn) return true;  // (orx_rollout_shape: whether a raise is needed and allowed)
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
-}
-
-// Threads per paired-rollout workgroup: kRolloutBlock, or 512 for a bank
-// whose tiles leave room for one workgroup per CU (more than half the LDS):
-// then the CU's one copy of the tiles serves 8 waves, two per SIMD, the
-// occupancy the paired plan's games per wave assume.  Env
-// ORX_ROLLOUT_THREADS (64 / 128 / 256, and 512 for banks) overrides.
-uint32_t pair_threads(const orx_cfg_t* cfg, uint32_t lanes, uint32_t lds_n) {
-  (void)lanes;
-  const char* e = getenv("ORX_ROLLOUT_THREADS");
-  const int x = e ? atoi(e) : 0;
-  if (x == 64 || x == 128 || x == 256 || (x == 512 && cfg->n_layouts > 0)) return (uint32_t)x;
-  if (cfg->n_layouts > 0 && 2ull * lds_n > device_lds_per_block()) return 512u;
-  return (uint32_t)kRolloutBlock;
-}
-
-// The form, games per wave and store policy of an orx_rollout launch.
-struct RolloutPlan {
-  bool paired;     // pair_rollout_kernel: two lanes per game
-  uint32_t lanes;  // games per wave
-  bool nt;         // nontemporal trajectory stores (whole-line row segments)
-};
-
-// The paired form: no dense NPCs (K <= 16), no bank, the RandomBot or StaircaseBot trajectory
-// forms (PM 1 / 2) and the RandomBot form with the character mechanics (PM 3,
-// round 4: each lane its own player's mana, experience, damage, max health
-// and items held; the game's items beside its NPCs in both lanes; every rare
-// tick through rare_tick), for batches the one-lane rule leaves below 64 games per
-// wave; its games per wave: two waves per SIMD -- counting the `concurrency`
-// launches that share the device (StreamShardedEngine's shards) -- until the
-// wave holds 32 games, at least 8 (C5's 8-GPU share, 16,384 games: 8 per
-// wave, 79 us per launch against 89 at 16 and 112 at 32; C2 at 4,096: 50
-// against 51; the bench's two 32,768-game C3 shards: 32 per wave, 96.6 us
-// per step against 158 at 16, four waves per SIMD where 156 VGPRs fit three).
-// ORX_ROLLOUT_LANES (games per wave) and ORX_ROLLOUT_PAIRED=0 override.
-RolloutPlan plan_rollout(const orx_cfg_t* cfg, int pm, uint32_t B, uint32_t concurrency) {
-  RolloutPlan p;
-  p.lanes = rollout_lanes(B);
-  // (its packed cells x | y << 8 need x, y < 256)
-  // a dungeon bank: PM 1 / 3, and PM 2 without separation damage, with the
-  // tiles staged in LDS (the paired form reads them only there)
-  const bool bank_ok = cfg->n_layouts == 0 ||
-                       (!(pm == 2 && (cfg->flags & ORX_EXT_SEPARATION_DAMAGE) != 0) && pm <= 3 &&
-                        bank_in_lds(cfg));
-  // StaircaseBots (PM 2) also pair where the one-lane rule fills whole
-  // waves, when the batch shares the device with another launch and the
-  // device's games come to at most four 32-game waves per SIMD: C5's 131,072
-  // games as two 65,536-game stream shards, 177-179 us per 128-tick step
-  // paired against 183-192 one-lane (242 / 254 with separation damage;
-  // profiles/r05_v1/c5_forms.jsonl)
-  const uint64_t simds4 = 4ull * 32ull * (uint64_t)device_simds();
-  const bool pm2_full = pm == 2 && p.lanes == 64u && concurrency >= 2 &&
-                        (uint64_t)B * concurrency <= simds4 && !lanes_override();
-  p.paired = ncap_for(cfg->n_npcs) != kDense && bank_ok && pm >= 1 && pm <= 6 &&
-             cfg->width <= 256 && cfg->height <= 256 && (p.lanes <= 32u || pm2_full) &&
-             paired_enabled();
-  if (p.paired) {
-    if (const int o = lanes_override()) {
-      p.lanes = o < 32 ? (uint32_t)o : 32u;
-    } else {
-      const uint64_t simds = (uint64_t)device_simds();
-      uint32_t L = 32;
-      while (L > 8 && (uint64_t)B * concurrency < 2 * simds * L) L >>= 1;
-      p.lanes = L;
-    }
-  }
-  p.nt = p.lanes * 4u >= 128u;  // a wave's row segment is a whole line
-  return p;
+template <class... P, class... A>
+int launch(const char* what, void (*kernel)(P...), int64_t n, hipStream_t s, const A&... args) {
+  hipLaunchKernelGGL(kernel, dim3(blocks_for((uint64_t)n, 64, kBlock)), dim3(kBlock), 0, s, args...);
+  return launch_status(what);
 }
 #endif  // ORX_HOST_TU
 
@@ -6091,7 +5939,7 @@ const char* orx_build_id(void) { return ORX_BUILD_ID; }
 
 int orx_rollout_lanes(int64_t n_games) {
   if (n_games <= 0 || n_games > 0x7FFFFFFFLL) return fail(ORX_EINVAL, "bad n_games");
-  return (int)rollout_lanes((uint32_t)n_games);
+  return (int)one_lane_lanes((uint32_t)n_games, read_env(), device());
 }
 
 const char* orx_last_error(void) { return g_err; }
@@ -6105,49 +5953,14 @@ int orx_rollout_shape(const orx_cfg_t* cfg, int32_t policy_p1, int32_t policy_p2
     return r;
   if (n_games <= 0 || n_games > 0x7FFFFFFFLL) return fail(ORX_EINVAL, "bad n_games");
   if (!out) return fail(ORX_EINVAL, "out is NULL");
-  const uint32_t B = (uint32_t)n_games;
-  out->threads_per_block = kBlock;
-  out->lds_bytes = 0;
-  if (moving_npcs(cfg)) {  // mov_rollout_kernel: one game per lane, mov_lanes per wave
-    out->games_per_wave = (int32_t)mov_lanes();
-    out->lanes_per_game = 1;
-    out->nontemporal = 1;
-    return ORX_OK;
-  }
-  if (cfg->rng == ORX_RNG_MT19937) {  // mt_rollout_kernel: one game per lane, full waves
-    out->games_per_wave = 64;
-    out->lanes_per_game = 1;
-    out->nontemporal = 1;
-    return ORX_OK;
-  }
-  int pm = rollout_pm(cfg, policy_p1, policy_p2, B, trajectory != 0);
-  RolloutPlan p = plan_rollout(cfg, pm, B, (uint32_t)concurrency);
-  if (!p.paired && pm >= 4) pm = 0;  // (the mixed-bot forms are paired only)
-  const uint64_t tiles = (uint64_t)cfg->n_layouts * (uint64_t)(cfg->width * cfg->height);
-  uint32_t lds_n = (cfg->n_layouts > 0 && bank_in_lds(cfg)) ? (uint32_t)tiles : 0u;
-  if (p.paired && !raise_lds(nullptr, lds_n)) {  // the launch's fallback (one lane, global tiles)
-    p.paired = false;
-    p.lanes = rollout_lanes(B);
-    p.nt = p.lanes * 4u >= 128u;
-    lds_n = 0u;
-  }
+  const Plan p = plan_rollout({cfg, policy_p1, policy_p2, (uint32_t)n_games, trajectory != 0,
+                               /*compact=*/false, (uint32_t)concurrency},
+                              read_env(), device());
   out->games_per_wave = (int32_t)p.lanes;
-  out->lanes_per_game = p.paired ? 2 : 1;
-  out->nontemporal = (pm != 0 && !p.nt) ? 0 : 1;
-  out->threads_per_block = (int32_t)(p.paired ? pair_threads(cfg, p.lanes, lds_n)
-                                              : rollout_threads(B, p.lanes));
-  uint32_t lds = p.paired ? lds_n : (uint32_t)((lds_n + 15u) & ~15u);
-  if (!p.paired) {  // as the one-lane launch: bitmaps, then tiles, dropped on a refused raise
-    uint32_t bits = 0;
-    if (ncap_for(cfg->n_npcs) == kDense && !getenv("ORX_NO_LDS_BITS")) {
-      const uint32_t bb = (uint32_t)((cfg->width * cfg->height + 31) / 32) * 4u;
-      const uint32_t per_block = (uint32_t)out->threads_per_block / 64u * p.lanes;
-      if ((uint64_t)lds + (uint64_t)per_block * bb <= device_lds_per_block()) bits = per_block * bb;
-    }
-    if (raise_lds(nullptr, lds + bits)) lds += bits;
-    if (!raise_lds(nullptr, lds)) lds = 0u;
-  }
-  out->lds_bytes = (int32_t)lds;
+  out->lanes_per_game = p.form == Form::kPaired ? 2 : 1;
+  out->nontemporal = p.nt ? 1 : 0;
+  out->threads_per_block = (int32_t)p.threads;
+  out->lds_bytes = (int32_t)p.lds_bytes;
   return ORX_OK;
 }
 
@@ -6176,10 +5989,8 @@ int orx_seed_mt(const orx_cfg_t* cfg, const orx_state_t* st, int64_t n_games, ui
     return fail(ORX_EINVAL, "seed + game id overflows 64 bits");
   if (n_games == 0) return ORX_OK;
   if ((r = check_state(cfg, st, false))) return r;
-  hipLaunchKernelGGL(mt_seed_kernel, grid_for(n_games), dim3(kBlock), 0, (hipStream_t)stream, *st,
-                     (uint32_t)n_games, seed, (uint32_t)game_offset,
-                     dstore_depths(cfg->max_ticks));
-  return launch_status("orx_seed_mt");
+  return launch("orx_seed_mt", mt_seed_kernel, n_games, (hipStream_t)stream, *st,
+                (uint32_t)n_games, seed, (uint32_t)game_offset, dstore_depths(cfg->max_ticks));
 }
 
 int orx_reset(const orx_cfg_t* cfg, const orx_state_t* st, const uint8_t* mask, int64_t n_games,
@@ -6193,21 +6004,14 @@ int orx_reset(const orx_cfg_t* cfg, const orx_state_t* st, const uint8_t* mask, 
   const Key k = make_key(seed);
   const int nc = ncap_for(cfg->n_npcs);
   const bool grid = cfg->n_layouts > 0;
-  if (cfg->rng == ORX_RNG_MT19937) {
+  const bool mt = cfg->rng == ORX_RNG_MT19937;
 #define ORX_RESET(N, G)                                                                         \
   if (nc == N && grid == G)                                                                     \
-    hipLaunchKernelGGL((mt_reset_kernel<N, G>), grid_for(B), dim3(kBlock), 0, s, *cfg, *st, mask, B);
-    ORX_NG_LIST(ORX_RESET)
-#undef ORX_RESET
-    return launch_status("orx_reset");
-  }
-#define ORX_RESET(N, G)                                                                         \
-  if (nc == N && grid == G)                                                                     \
-    hipLaunchKernelGGL((reset_kernel<N, G>), grid_for(B), dim3(kBlock), 0, s, *cfg, *st, mask, B, \
-                       k, off);
+    return mt ? launch("orx_reset", mt_reset_kernel<N, G>, B, s, *cfg, *st, mask, B)            \
+              : launch("orx_reset", reset_kernel<N, G>, B, s, *cfg, *st, mask, B, k, off);
   ORX_NG_LIST(ORX_RESET)
 #undef ORX_RESET
-  return launch_status("orx_reset");
+  return fail(ORX_EIO, "orx_reset: no kernel instance for this configuration");
 }
 
 static int launch_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
@@ -6226,45 +6030,29 @@ static int launch_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t
   const int nc = ncap_for(cfg->n_npcs);
   const bool grid = cfg->n_layouts > 0;
   const bool mt = cfg->rng == ORX_RNG_MT19937;
+#define ORX_STEP_ARGS B, s, *cfg, *st, actions, B, k, off, events, n_events
+#define ORX_STEP(NC, E, G, MOV)                                                                 \
+  if (nc == NC && ev == E && grid == G)                                                         \
+    return mt ? launch(name, mt_step_kernel<NC, E, G, MOV>, ORX_STEP_ARGS)                      \
+              : launch(name, step_kernel<NC, E, G, true, MOV>, ORX_STEP_ARGS);
+#define ORX_STEP_MOV(NC, E, G) ORX_STEP(NC, E, G, true)
+#define ORX_STEP_STAY(NC, E, G) ORX_STEP(NC, E, G, false)
+#define ORX_STEP_REF(NC)                                                                        \
+  if (nc == NC) return launch(name, step_kernel<NC, false, false, false>, ORX_STEP_ARGS);
   if (moving_npcs(cfg)) {  // the ordered tick with the enemy AI
-#define ORX_STEP(NC, E, G)                                                                      \
-  if (nc == NC && ev == E && grid == G) {                                                      \
-    if (mt)                                                                                     \
-      hipLaunchKernelGGL((mt_step_kernel<NC, E, G, true>), grid_for(B), dim3(kBlock), 0, s,     \
-                         *cfg, *st, actions, B, k, off, events, n_events);                      \
-    else                                                                                        \
-      hipLaunchKernelGGL((step_kernel<NC, E, G, true, true>), grid_for(B), dim3(kBlock), 0, s,  \
-                         *cfg, *st, actions, B, k, off, events, n_events);                      \
-    return launch_status(name);                                                                \
-  }
-    ORX_MOV_STEP_LIST(ORX_STEP)
-#undef ORX_STEP
+    ORX_MOV_STEP_LIST(ORX_STEP_MOV)
     return fail(ORX_EIO, "orx_step: no moving-NPC kernel instance for this configuration");
   }
-  if (!ev && !grid && !mt && cfg->flags == 0 && nc != kDense) {  // the reference's rules
-    if (nc == 0)
-      hipLaunchKernelGGL((step_kernel<0, false, false, false>), grid_for(B), dim3(kBlock), 0, s,
-                         *cfg, *st, actions, B, k, off, events, n_events);
-    else if (nc == 8)
-      hipLaunchKernelGGL((step_kernel<8, false, false, false>), grid_for(B), dim3(kBlock), 0, s,
-                         *cfg, *st, actions, B, k, off, events, n_events);
-    else
-      hipLaunchKernelGGL((step_kernel<16, false, false, false>), grid_for(B), dim3(kBlock), 0, s,
-                         *cfg, *st, actions, B, k, off, events, n_events);
-    return launch_status(name);
+  if (!ev && !grid && !mt && cfg->flags == 0) {  // the reference's rules (no dense instance)
+    ORX_STEP_REF_LIST(ORX_STEP_REF)
   }
-#define ORX_STEP(NC, E, G)                                                                      \
-  if (nc == NC && ev == E && grid == G) {                                                      \
-    if (mt)                                                                                     \
-      hipLaunchKernelGGL((mt_step_kernel<NC, E, G>), grid_for(B), dim3(kBlock), 0, s, *cfg, *st, \
-                         actions, B, k, off, events, n_events);                                 \
-    else                                                                                        \
-      hipLaunchKernelGGL((step_kernel<NC, E, G>), grid_for(B), dim3(kBlock), 0, s, *cfg, *st,   \
-                         actions, B, k, off, events, n_events);                                 \
-  }
-  ORX_STEP_LIST(ORX_STEP)
+  ORX_STEP_LIST(ORX_STEP_STAY)
+#undef ORX_STEP_REF
+#undef ORX_STEP_STAY
+#undef ORX_STEP_MOV
 #undef ORX_STEP
-  return launch_status(name);
+#undef ORX_STEP_ARGS
+  return fail(ORX_EIO, "orx_step: no kernel instance for this configuration");
 }
 
 int orx_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions, int64_t n_games,
@@ -6309,86 +6097,42 @@ int orx_step_n_ex(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* act
   const Key k = make_key(seed);
   const int nc = ncap_for(cfg->n_npcs);
   const bool grid = cfg->n_layouts > 0;
-  // register NPCs on empty dungeons: the rollout's tick on the logged pairs
-  // (ORX_STEP_N_GENERIC=1 forces the generic one, for A/B runs and tests)
-  const char* gen_env = getenv("ORX_STEP_N_GENERIC");
-  // (the buffer-store rows address one tick's rows with 32-bit offsets)
-  const bool rows_fit = (uint64_t)B * ORX_OBS_FIELDS * 4u < (1ull << 31);
-  if (moving_npcs(cfg)) {
-#define ORX_STEP_N(N, G)                                                                        \
-    if (nc == N && grid == G) {                                                                 \
-      hipLaunchKernelGGL((step_n_kernel<N, G, true>), grid_for(B), dim3(kBlock), 0, s, *cfg,    \
-                         *st, actions, n_ticks, obs, B, k, off, obs_format);                    \
-      return launch_status("orx_step_n");                                                      \
-    }
-    ORX_MOV_NG_LIST(ORX_STEP_N)
-#undef ORX_STEP_N
-    return fail(ORX_EIO, "orx_step_n: no moving-NPC kernel instance for this configuration");
-  }
-  if (!grid && nc != kDense && rows_fit && !(gen_env && gen_env[0] == '1')) {
-    const int rows = obs ? (obs_format == ORX_OBS_COMPACT ? 2 : 1) : 0;
-    // the paired form (pair_rollout_kernel PM 6: two lanes per game, the
-    // rollout's paired tick on the logged moves) for rows given under the
-    // reference's rules, at any batch: two waves per SIMD over the device's
-    // concurrent launches until the wave holds 32 games (C3, 65,536 games x
-    // 128 ticks, int32 rows: 103-104 us against 114-116 for the one-lane
-    // replay_kernel; as two 32,768-game stream shards at 32 games per wave
-    // 85-86 us, at 16 -- the plan without the concurrency -- 207,
-    // profiles/r06_v3 / r06_v4 ab_replay_paired.jsonl).  Env
-    // ORX_REPLAY_PAIRED=0 keeps the one-lane form, for measurements.
-    const char* pe = getenv("ORX_REPLAY_PAIRED");
-    RolloutPlan pl;
-    bool paired = rows != 0 && cfg->flags == 0 && cfg->n_layouts == 0 && paired_enabled() &&
-                  cfg->width <= 256 && cfg->height <= 256 && !(pe && pe[0] == '0');
-    if (paired) {
-      const uint64_t simds = (uint64_t)device_simds();
-      uint32_t L = 32;
-      while (L > 8 && (uint64_t)B * (uint32_t)concurrency < 2 * simds * L) L >>= 1;
-      if (const int o = lanes_override()) L = o < 32 ? (uint32_t)o : 32u;
-      pl.lanes = L;
-      pl.nt = L * 4u >= 128u;
-      pl.paired = true;
-    }
-    if (paired) {
-      const uint32_t lanes = pl.lanes, threads = (uint32_t)kRolloutBlock;
-      const uint32_t per_block = threads / 64u * lanes;
-      const dim3 blocks((B + per_block - 1) / per_block);
+  const int rows = obs ? (obs_format == ORX_OBS_COMPACT ? 2 : 1) : 0;
+  const Plan p = plan_step_n(cfg, B, rows, (uint32_t)concurrency, read_env(), device());
+#define ORX_STEP_N(N, G, MOV)                                                                   \
+  if (nc == N && grid == G)                                                                     \
+    return launch("orx_step_n", step_n_kernel<N, G, MOV>, p, s, *cfg, *st, actions, n_ticks,    \
+                  obs, B, k, off, obs_format);
+#define ORX_STEP_N_MOV(N, G) ORX_STEP_N(N, G, true)
+#define ORX_STEP_N_STAY(N, G) ORX_STEP_N(N, G, false)
+#define ORX_PAIR_LOG(N, P, A, S, C, G)                                                          \
+  if (nc == N && (A == kStreamAux) == p.nt && C == (rows == 2))                                 \
+    return launch("orx_step_n", pair_rollout_kernel<N, P, A, S, C, G>, p, s, *cfg, *st,         \
+                  n_ticks, obs, log, B, k, off, p.lanes, 0u);
+#define ORX_REPLAY(N, R, E)                                                                     \
+  if (nc == N && rows == R && (cfg->flags != 0) == E)                                           \
+    return launch("orx_step_n", replay_kernel<N, R, E>, p, s, *cfg, *st, actions, n_ticks, obs, \
+                  B, k, off, p.lanes);
+  switch (p.form) {
+    case Form::kMoving:
+      ORX_MOV_NG_LIST(ORX_STEP_N_MOV)
+      return fail(ORX_EIO, "orx_step_n: no moving-NPC kernel instance for this configuration");
+    case Form::kPaired: {  // the rollout's paired tick on the logged moves
       int8_t* log = const_cast<int8_t*>(actions);  // (PM 6 reads it; the form never writes it)
-#define ORX_PAIR_LOG(N, A, C)                                                                   \
-      if (nc == N && (A == kStreamAux) == pl.nt && C == (rows == 2)) {                          \
-        hipLaunchKernelGGL((pair_rollout_kernel<N, 6, A, false, C, false>), blocks,              \
-                           dim3(threads), 0, s, *cfg, *st, n_ticks, obs, log, B, k, off, lanes,  \
-                           0u);                                                                 \
-        return launch_status("orx_step_n");                                                    \
-      }
-      ORX_PAIR_LOG(0, kStreamAux, false) ORX_PAIR_LOG(0, kPartialAux, false)
-      ORX_PAIR_LOG(0, kStreamAux, true) ORX_PAIR_LOG(0, kPartialAux, true)
-      ORX_PAIR_LOG(8, kStreamAux, false) ORX_PAIR_LOG(8, kPartialAux, false)
-      ORX_PAIR_LOG(8, kStreamAux, true) ORX_PAIR_LOG(8, kPartialAux, true)
-      ORX_PAIR_LOG(16, kStreamAux, false) ORX_PAIR_LOG(16, kPartialAux, false)
-      ORX_PAIR_LOG(16, kStreamAux, true) ORX_PAIR_LOG(16, kPartialAux, true)
-#undef ORX_PAIR_LOG
+      ORX_PAIR_LIST_L(ORX_PAIR_LOG, 0) ORX_PAIR_LIST_L(ORX_PAIR_LOG, 8)
+      ORX_PAIR_LIST_L(ORX_PAIR_LOG, 16)
       return fail(ORX_EIO, "orx_step_n: no paired replay instance for this plan");
     }
-    const uint32_t lanes = rollout_lanes(B);  // games per wave, as the rollout's plan
-    const uint64_t threads = (((uint64_t)B + lanes - 1) / lanes) * 64u;
-    const dim3 g((unsigned)((threads + kRolloutBlock - 1) / kRolloutBlock));
-#define ORX_REPLAY(N, R, E)                                                                     \
-    if (nc == N && rows == R && (cfg->flags != 0) == E) {                                       \
-      hipLaunchKernelGGL((replay_kernel<N, R, E>), g, dim3(kRolloutBlock), 0, s, *cfg, *st,     \
-                         actions, n_ticks, obs, B, k, off, lanes);                              \
-      return launch_status("orx_step_n");                                                      \
-    }
-    ORX_REPLAY_LIST(ORX_REPLAY)
+    case Form::kReplay:  // ... its one-lane tick
+      ORX_REPLAY_LIST(ORX_REPLAY)
+      break;
+    default:
+      ORX_NG_LIST(ORX_STEP_N_STAY)
+  }
 #undef ORX_REPLAY
-  }
-#define ORX_STEP_N(N, G)                                                                        \
-  if (nc == N && grid == G) {                                                                   \
-    hipLaunchKernelGGL((step_n_kernel<N, G>), grid_for(B), dim3(kBlock), 0, s, *cfg, *st,       \
-                       actions, n_ticks, obs, B, k, off, obs_format);                           \
-    return launch_status("orx_step_n");                                                        \
-  }
-  ORX_NG_LIST(ORX_STEP_N)
+#undef ORX_PAIR_LOG
+#undef ORX_STEP_N_STAY
+#undef ORX_STEP_N_MOV
 #undef ORX_STEP_N
   return fail(ORX_EIO, "orx_step_n: no kernel instance for this configuration");
 }
@@ -6404,14 +6148,11 @@ int orx_policy(const orx_cfg_t* cfg, const orx_state_t* st, int32_t policy_p1, i
   if ((r = check_state(cfg, st, false))) return r;
   if (!actions) return fail(ORX_EINVAL, "actions is NULL");
   const uint32_t B = (uint32_t)n_games, off = (uint32_t)game_offset;
-  if (cfg->rng == ORX_RNG_MT19937) {
-    hipLaunchKernelGGL(mt_policy_kernel, grid_for(B), dim3(kBlock), 0, (hipStream_t)stream, *st,
-                       policy_p1, policy_p2, actions, B);
-    return launch_status("orx_policy");
-  }
-  hipLaunchKernelGGL(policy_kernel, grid_for(B), dim3(kBlock), 0, (hipStream_t)stream, *st,
-                     policy_p1, policy_p2, actions, B, make_key(seed), off);
-  return launch_status("orx_policy");
+  if (cfg->rng == ORX_RNG_MT19937)
+    return launch("orx_policy", mt_policy_kernel, B, (hipStream_t)stream, *st, policy_p1,
+                  policy_p2, actions, B);
+  return launch("orx_policy", policy_kernel, B, (hipStream_t)stream, *st, policy_p1, policy_p2,
+                actions, B, make_key(seed), off);
 }
 
 int orx_env_step(const orx_cfg_t* cfg, const orx_state_t* st, const void* actions,
@@ -6456,38 +6197,22 @@ int orx_env_step_ex(const orx_cfg_t* cfg, const orx_state_t* st, const void* act
   const Key k = make_key(seed);
   const int nc = ncap_for(cfg->n_npcs);
   const bool grid = cfg->n_layouts > 0;
-  // the rows through LDS and 16-byte stores when obs is 16-byte aligned (a
-  // torch allocation is; a view may not be: then direct stores), env
-  // ORX_ENV_DIRECT_ROWS=1: direct stores, for measurements
-  const char* dr = getenv("ORX_ENV_DIRECT_ROWS");
-  const int32_t lds_rows = ((dr && dr[0] == '1') || ((uintptr_t)obs & 15u) != 0) ? 0 : 1;
-  // games per wave: 64, or 32 where that still leaves at most two waves per
-  // SIMD (env ORX_ENV_LANES = 64 / 32 overrides, for measurements)
-  const char* le = getenv("ORX_ENV_LANES");
-  const int lo = le ? atoi(le) : 0;
-  const uint32_t env_lanes = (lo == 32 || lo == 64) ? (uint32_t)lo : 64u;
-  const uint32_t per_blk = (uint32_t)kBlock / 64u * env_lanes;
-  const dim3 env_grid((unsigned)((B + per_blk - 1) / per_blk));
-  if (moving_npcs(cfg)) {
-#define ORX_ENV(N, G)                                                                           \
-    if (nc == N && grid == G) {                                                                 \
-      hipLaunchKernelGGL((env_step_kernel<N, G, true, true>), env_grid, dim3(kBlock), 0, s,     \
-                         *cfg, *st, actions, action_bytes, action_cols, policy_p2, act, obs,    \
-                         reward, done, status, bad_actions, B, k, off, lds_rows, env_lanes);    \
-      return launch_status("orx_env_step");                                                    \
-    }
-    ORX_MOV_NG_LIST(ORX_ENV)
-#undef ORX_ENV
+  const Plan p = plan_env_step(cfg, B, ((uintptr_t)obs & 15u) == 0, read_env());
+  const int32_t lds_rows = p.lds_rows ? 1 : 0;
+#define ORX_ENV(N, G, X, MOV)                                                                   \
+  if (nc == N && grid == G && (cfg->flags == 0 || X))                                           \
+    return launch("orx_env_step", env_step_kernel<N, G, X, MOV>, p, s, *cfg, *st, actions,      \
+                  action_bytes, action_cols, policy_p2, act, obs, reward, done, status,         \
+                  bad_actions, B, k, off, lds_rows, p.lanes);
+#define ORX_ENV_MOV(N, G) ORX_ENV(N, G, true, true)
+#define ORX_ENV_STAY(N, G, X) ORX_ENV(N, G, X, false)
+  if (p.form == Form::kMoving) {
+    ORX_MOV_NG_LIST(ORX_ENV_MOV)
     return fail(ORX_EIO, "orx_env_step: no moving-NPC kernel instance for this configuration");
   }
-#define ORX_ENV(N, G, X)                                                                        \
-  if (nc == N && grid == G && (cfg->flags == 0 || X)) {                                        \
-    hipLaunchKernelGGL((env_step_kernel<N, G, X>), env_grid, dim3(kBlock), 0, s, *cfg, *st,      \
-                       actions, action_bytes, action_cols, policy_p2, act, obs, reward, done,   \
-                       status, bad_actions, B, k, off, lds_rows, env_lanes);                    \
-    return launch_status("orx_env_step");                                                      \
-  }
-  ORX_ENV_LIST(ORX_ENV)
+  ORX_ENV_LIST(ORX_ENV_STAY)
+#undef ORX_ENV_STAY
+#undef ORX_ENV_MOV
 #undef ORX_ENV
   return fail(ORX_EIO, "orx_env_step: no kernel instance for this configuration");
 }
@@ -6528,122 +6253,62 @@ int orx_rollout_ex(const orx_cfg_t* cfg, const orx_state_t* st, int32_t policy_p
   const uint32_t B = (uint32_t)n_games, off = (uint32_t)game_offset;
   const hipStream_t s = (hipStream_t)stream;
   const Key k = make_key(seed);
-  // the buffer-addressed trajectory forms need one tick's obs rows below 2 GiB
   const bool grid = cfg->n_layouts > 0;
   const int nc = ncap_for(cfg->n_npcs);
-  if (moving_npcs(cfg)) {  // the ordered tick with the enemy AI, one lane per game
-    const bool mt = cfg->rng == ORX_RNG_MT19937;
-    const uint32_t lanes = mov_lanes();
-    const uint64_t threads = (((uint64_t)B + lanes - 1) / lanes) * 64u;
-    const dim3 g((unsigned)((threads + kBlock - 1) / kBlock));
-#define ORX_ROLLOUT(N, G, M)                                                                    \
-    if (nc == N && grid == G && mt == M) {                                                      \
-      hipLaunchKernelGGL((mov_rollout_kernel<N, G, M>), g, dim3(kBlock), 0, s, *cfg, *st,       \
-                         policy_p1, policy_p2, n_ticks, obs, act, B, k, off, obs_format, lanes); \
-      return launch_status("orx_rollout");                                                     \
-    }
-    ORX_MOV_ROLLOUT_LIST(ORX_ROLLOUT)
-#undef ORX_ROLLOUT
-    return fail(ORX_EIO, "orx_rollout: no moving-NPC kernel instance for this configuration");
-  }
-  if (cfg->rng == ORX_RNG_MT19937) {
-#define ORX_ROLLOUT(N, G)                                                                       \
+  const bool mt = cfg->rng == ORX_RNG_MT19937;
+  const bool sep = (cfg->flags & ORX_EXT_SEPARATION_DAMAGE) != 0;
+  constexpr int kRefused = 1;  // (no ORX_* code: the runtime refused the plan's LDS limit raise)
+#define ORX_MOV_ROLLOUT(N, G, M)                                                                \
+  if (nc == N && grid == G && mt == M)                                                          \
+    return launch("orx_rollout", mov_rollout_kernel<N, G, M>, p, s, *cfg, *st, policy_p1,       \
+                  policy_p2, n_ticks, obs, act, B, k, off, obs_format, p.lanes);
+#define ORX_MT_ROLLOUT(N, G)                                                                    \
   if (nc == N && grid == G)                                                                     \
-    hipLaunchKernelGGL((mt_rollout_kernel<N, G>), grid_for(B), dim3(kBlock), 0, s, *cfg, *st,   \
-                       policy_p1, policy_p2, n_ticks, obs, act, B, k, off, obs_format);
-    ORX_NG_LIST(ORX_ROLLOUT)
-#undef ORX_ROLLOUT
-    return launch_status("orx_rollout");
-  }
-  int pm = rollout_pm(cfg, policy_p1, policy_p2, B, obs && act);
-  // compact rows: the buffer-store forms of PM 1 / 2 without a bank or dense
-  // NPCs have compact instances; every other launch takes the generic form,
-  // whose writer reads the format at run time
-  if (cf && (pm >= 3 || grid || nc == kDense)) pm = 0;
-  RolloutPlan plan = plan_rollout(cfg, pm, B, (uint32_t)concurrency);
-  if (!plan.paired && pm >= 4) pm = 0;  // (the mixed-bot forms are paired only)
-  // dynamic LDS: the bank's tiles when they fit the device's per-workgroup
-  // limit (160 KiB on gfx950, above 64 KiB with the opt-in raise)
-  const uint64_t tiles = grid ? (uint64_t)cfg->n_layouts * (uint64_t)(cfg->width * cfg->height) : 0;
-  uint32_t lds_n = (grid && bank_in_lds(cfg)) ? (uint32_t)tiles : 0u;
-  const uint32_t lds_max = device_lds_per_block();
-  // the paired form (two lanes per game, pair_rollout_kernel): K <= 16 NPCs
-  // in registers, a bank only with its tiles in LDS (the paired tick reads
-  // them nowhere else), the RandomBot / StaircaseBot / character trajectory
-  // forms, at most 32 games per wave (env ORX_ROLLOUT_PAIRED=0 turns it off)
-  if (plan.paired) {
-    if (grid && !lds_n) return fail(ORX_EIO, "orx_rollout: a paired bank launch without LDS tiles");
-    const uint32_t lanes = plan.lanes;
-    const uint32_t threads = pair_threads(cfg, lanes, lds_n);
-    const uint32_t per_block = threads / 64u * lanes;
-    const bool nt = plan.nt;
-    const dim3 blocks((B + per_block - 1) / per_block);
-    const bool sepd = pm == 2 && (cfg->flags & ORX_EXT_SEPARATION_DAMAGE) != 0;
-    // a refused limit raise (above the default 64 KiB) drops the launch to
-    // the one-lane form below with the tiles in global memory -- never a
-    // paired launch without them
-    bool refused = false;
+    return launch("orx_rollout", mt_rollout_kernel<N, G>, p, s, *cfg, *st, policy_p1,           \
+                  policy_p2, n_ticks, obs, act, B, k, off, obs_format);
 #define ORX_PAIR(N, P, A, S, C, G)                                                              \
-    if (nc == N && pm == P && (A == kStreamAux) == nt && S == sepd && C == cf && G == grid) {   \
-      auto* kfn = &pair_rollout_kernel<N, P, A, S, C, G>;                                       \
-      if (!raise_lds(reinterpret_cast<const void*>(kfn), lds_n)) {                              \
-        refused = true;                                                                         \
-      } else {                                                                                  \
-        hipLaunchKernelGGL(kfn, blocks, dim3(threads), lds_n, s, *cfg, *st, n_ticks, obs, act, B, \
-                           k, off, lanes, lds_n);                                               \
-        return launch_status("orx_rollout");                                                    \
-      }                                                                                         \
-    }
-    ORX_PAIR_LIST(ORX_PAIR)
-#undef ORX_PAIR
-    if (!refused) return fail(ORX_EIO, "orx_rollout: no paired kernel instance for this plan");
-    plan.paired = false;
-    if (pm >= 4) pm = 0;
-    plan.lanes = rollout_lanes(B);
-    plan.nt = plan.lanes * 4u >= 128u;
-    lds_n = 0u;
-  }
-  const uint32_t lanes = plan.lanes;
-  const uint32_t threads = rollout_threads(B, lanes);
-  const uint32_t per_block = threads / 64u * lanes;
-  const bool nt = plan.nt;
-  uint32_t lds = (uint32_t)((lds_n + 15u) & ~15u);
-  // dense NPCs: one occupancy bitmap per game of the block after the tiles,
-  // when they fit the device's per-workgroup LDS (a workgroup may take all
-  // 160 KiB on gfx950); the bitmaps are an optimization -- without them the
-  // kernel reads the occupancy grid from HBM -- so a part with less LDS, or
-  // a refused limit raise, launches without them instead of failing
-  uint32_t lds_bits = 0;
-  if (nc == kDense && !getenv("ORX_NO_LDS_BITS")) {
-    const uint32_t bb = (uint32_t)((cfg->width * cfg->height + 31) / 32) * 4u;
-    if ((uint64_t)lds + (uint64_t)per_block * bb <= lds_max) {
-      lds_bits = bb;
-      lds += per_block * bb;
-    }
-  }
-  // a refused limit raise: first without the bitmaps, then without the tiles
-  // (rollout_kernel reads a bank's tiles from global memory when lds_n is 0)
+  if (nc == N && p.pm == P && (A == kStreamAux) == p.nt && S == (P == 2 && sep) && C == cf &&   \
+      G == grid)                                                                                \
+    return !raise_lds(pair_rollout_kernel<N, P, A, S, C, G>, p) ? kRefused                      \
+           : launch("orx_rollout", pair_rollout_kernel<N, P, A, S, C, G>, p, s, *cfg, *st,      \
+                    n_ticks, obs, act, B, k, off, p.lanes, p.lds_n);
 #define ORX_ROLLOUT_AC(N, P, G, A, C)                                                           \
-  if (nc == N && pm == P && grid == G && (P == 0 || (A == kStreamAux) == nt) &&                 \
-      (P == 0 || C == cf)) {                                                                    \
-    const void* kfn = reinterpret_cast<const void*>(&rollout_kernel<N, P, G, A, C>);            \
-    if (!raise_lds(kfn, lds) && lds_bits) {                                                     \
-      lds -= per_block * lds_bits;                                                              \
-      lds_bits = 0;                                                                             \
-    }                                                                                           \
-    if (!raise_lds(kfn, lds)) {                                                                 \
-      lds_n = 0u;                                                                               \
-      lds = 0u;                                                                                 \
-    }                                                                                           \
-    hipLaunchKernelGGL((rollout_kernel<N, P, G, A, C>), dim3((B + per_block - 1) / per_block),  \
-                       dim3(threads), lds, s, *cfg, *st,                                        \
-                       policy_p1, policy_p2, n_ticks, obs, act, B, k, off, lanes, lds_n,        \
-                       lds_bits, obs_format);                                                   \
-    return launch_status("orx_rollout");                                                        \
-  }
-  ORX_ROLLOUT_LIST(ORX_ROLLOUT_AC)
+  if (nc == N && p.pm == P && grid == G && (A == kStreamAux) == p.nt && (P == 0 || C == cf))    \
+    return !raise_lds(rollout_kernel<N, P, G, A, C>, p) ? kRefused                              \
+           : launch("orx_rollout", rollout_kernel<N, P, G, A, C>, p, s, *cfg, *st, policy_p1,   \
+                    policy_p2, n_ticks, obs, act, B, k, off, p.lanes, p.lds_n, p.lds_bits,      \
+                    obs_format);
+  // launches the instance the plan names
+  auto run = [&](const Plan& p) -> int {
+    switch (p.form) {
+      case Form::kMoving:  // the ordered tick with the enemy AI, one lane per game
+        ORX_MOV_ROLLOUT_LIST(ORX_MOV_ROLLOUT)
+        return fail(ORX_EIO, "orx_rollout: no moving-NPC kernel instance for this configuration");
+      case Form::kMt:
+        ORX_NG_LIST(ORX_MT_ROLLOUT)
+        break;
+      case Form::kPaired:  // (the paired tick reads a bank's tiles nowhere but in LDS)
+        if (grid && !p.lds_n)
+          return fail(ORX_EIO, "orx_rollout: a paired bank launch without LDS tiles");
+        ORX_PAIR_LIST(ORX_PAIR)
+        return fail(ORX_EIO, "orx_rollout: no paired kernel instance for this plan");
+      default:
+        ORX_ROLLOUT_LIST(ORX_ROLLOUT_AC)
+    }
+    return fail(ORX_EIO, "orx_rollout: no rollout kernel instance for this plan");
+  };
 #undef ORX_ROLLOUT_AC
-  return fail(ORX_EIO, "orx_rollout: no rollout kernel instance for this plan");
+#undef ORX_PAIR
+#undef ORX_MT_ROLLOUT
+#undef ORX_MOV_ROLLOUT
+  const RolloutRequest q{cfg, policy_p1, policy_p2, B, obs && act, cf, (uint32_t)concurrency};
+  const Env env = read_env();
+  const Device dev = device();
+  r = run(plan_rollout(q, env, dev));
+  // a refused raise: the plan without one (one lane per game, no bitmaps,
+  // the tiles in global memory -- never a paired launch without them)
+  if (r == kRefused) r = run(plan_rollout(q, env, dev, /*allow_raise=*/false));
+  return r;
 }
 
 #ifdef ORX_STAMPS
@@ -6678,15 +6343,9 @@ int orx_dungeon_spawn(const orx_cfg_t* cfg, const orx_state_t* st, const uint32_
     bank.bank_ground = st->bank_ground;
     bank.bank_meta = st->bank_meta;
   }
-  if (cfg->n_layouts > 0)
-    hipLaunchKernelGGL(stairs_kernel<true>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream,
-                       *cfg, bank, game_ids, episodes, depths, gens, sx, sy, layout, (uint32_t)n,
-                       make_key(seed));
-  else
-    hipLaunchKernelGGL(stairs_kernel<false>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream,
-                       *cfg, bank, game_ids, episodes, depths, gens, sx, sy, layout, (uint32_t)n,
-                       make_key(seed));
-  return launch_status("orx_dungeon_spawn");
+  return launch("orx_dungeon_spawn", cfg->n_layouts > 0 ? stairs_kernel<true> : stairs_kernel<false>,
+                n, (hipStream_t)stream, *cfg, bank, game_ids, episodes, depths, gens, sx, sy,
+                layout, (uint32_t)n, make_key(seed));
 }
 
 int orx_dungeon_stairs(const orx_cfg_t* cfg, const uint32_t* game_ids, const int32_t* episodes,

@@ -277,7 +277,7 @@ def test_engine_view_checks_come_before_the_library():
 def test_view_symbol_and_export_lists(engine_lib):
     """orx_view is exported by liborx.so and bound from a list of its own;
     _lib.EXPORTS still equals what orx.h declares, and the build id hashes
-    the view's two files and the queries' shared header."""
+    the view's two files, the queries' shared header and the launch plan."""
     from optimax_rogue_amd import _lib, build
     assert _lib.VIEW_EXPORTS == ("orx_view",)
     assert hasattr(engine_lib, "orx_view")
@@ -294,9 +294,11 @@ def test_view_symbol_and_export_lists(engine_lib):
     assert _lib.build_id() == build.source_id()
     import hashlib
     h = hashlib.sha256()
-    for p in (build.SRC, build.HDR, build.VIEW_SRC, build.VIEW_HDR, build.QUERY_HDR):
+    for p in (build.SRC, build.HDR, build.VIEW_SRC, build.VIEW_HDR, build.QUERY_HDR,
+              build.PLAN_HDR):
         h.update(open(p, "rb").read())
     assert build.source_id() == h.hexdigest()[:16]
+    assert os.path.basename(build.PLAN_HDR) == "orx_plan.h"
     assert os.path.basename(build.QUERY_HDR) == "orx_query.h"
     assert os.path.basename(build.VIEW_SRC) == "orx_view.hip"
     assert os.path.basename(build.VIEW_HDR) == "orx_view.h"
