@@ -937,6 +937,12 @@ struct PhiloxSrc {
   static constexpr bool kMt = false;
   Key key;
   uint32_t game, ep;
+  // the game's source in episode ep; open / close: nothing to fetch or write back
+  static __device__ __forceinline__ PhiloxSrc make(Key key, uint32_t game, uint32_t ep) {
+    return PhiloxSrc{key, game, ep};
+  }
+  __device__ __forceinline__ void open(const orx_state_t&, const Cfg&, uint32_t, uint32_t) {}
+  __device__ __forceinline__ void close() const {}
   __device__ __forceinline__ Stream init() const {
     Stream s;
     s.init(game, ep, 0, tag(PUR_INIT, 0));
@@ -965,6 +971,7 @@ struct MtSrc {
   MtStream py, np;  // CPython random (bots, shuffles), numpy RandomState (world)
   int32_t* ds;      // this game's dstore column, stride B: [2][N][2]
   uint32_t B, dmask;  // dmask = N - 1 (N a power of two)
+  static __device__ __forceinline__ MtSrc make(Key, uint32_t, uint32_t) { return MtSrc{}; }
   __device__ __forceinline__ void open(const orx_state_t& st, const Cfg& c, uint32_t B_,
                                        uint32_t i) {
     py.open(st.mt_py, B_, i);
@@ -1419,6 +1426,19 @@ __device__ __forceinline__ void policy_pair(Key key, uint32_t game, uint32_t ep,
   bool err = false;
   if (need) moves_from_block(tb, need, key, game, ep, tick, r0, r1, err);
   assign_moves(pol1, pol2, r0, r1, p1, p2, a1, a2);
+}
+
+// Stock-seed mode (cfg.rng = ORX_RNG_MT19937):
+// RandomBot.move = random.choice(list(Move)) = Move(1 + _randbelow(5))
+// (randombot.py:21) from the game's CPython stream; StaircaseBot as usual.
+__device__ __forceinline__ void mt_policy_pair(MtStream& py, int32_t pol1, int32_t pol2,
+                                               const Player& p1, const Player& p2, int32_t& a1,
+                                               int32_t& a2, bool& err) {
+  int32_t r[2] = {ORX_MOVE_STAY, ORX_MOVE_STAY};
+  int nr = 0;
+  if (pol1 == ORX_POLICY_RANDOM) r[nr++] = 1 + (int32_t)py_randbelow(py, Key{0, 0}, 5u, err);
+  if (pol2 == ORX_POLICY_RANDOM) r[nr++] = 1 + (int32_t)py_randbelow(py, Key{0, 0}, 5u, err);
+  assign_moves(pol1, pol2, r[0], r[1], p1, p2, a1, a2);
 }
 
 // ---------------------------------------------------------------------------
@@ -2851,9 +2871,10 @@ __device__ __forceinline__ uint16_t pack_actions(int32_t a1, int32_t a2) {
 }
 
 // ---------------------------------------------------------------------------
-// Kernels (NCAP = NPC slot capacity: 0, 8 or 16)
+// Kernels (NCAP = NPC slot capacity: 0, 8 or 16; MT: stock-seed mode, cfg.rng
+// = ORX_RNG_MT19937, the draws from the game's own streams -- MtSrc)
 // ---------------------------------------------------------------------------
-template <int NCAP, bool GRID>
+template <int NCAP, bool GRID, bool MT = false>
 __global__ void __launch_bounds__(256) reset_kernel(orx_cfg_t hc, orx_state_t st,
                                                     const uint8_t* __restrict__ mask, uint32_t B,
                                                     Key key, uint32_t off) {
@@ -2861,11 +2882,16 @@ __global__ void __launch_bounds__(256) reset_kernel(orx_cfg_t hc, orx_state_t st
   if (i >= B) return;
   if (mask && !mask[i]) return;
   const Cfg c = make_cfg(hc, st);
+  // (declared first: where the compiler has always had the Philox source)
+  std::conditional_t<MT, MtSrc, PhiloxSrc> src =
+      decltype(src)::make(key, off + i, MT ? 0u : (uint32_t)st.episode[i]);
   Player p1, p2;
   Npcs<NCAP> npc;
   npc.bind(st, c, B, i);
   int32_t tick, status;
-  setup_game<NCAP, GRID>(c, key, off + i, (uint32_t)st.episode[i], p1, p2, npc, tick, status);
+  src.open(st, c, B, i);
+  setup_game<NCAP, GRID>(c, key, src, p1, p2, npc, tick, status);
+  src.close();  // (stock-seed mode: the streams' indices, before the state)
   store_players<GRID>(st, B, i, p1, p2, true);
   Items<NCAP> items;
   items.clear();
@@ -3014,7 +3040,10 @@ __global__ void __launch_bounds__(256) step_kernel(orx_cfg_t hc, orx_state_t st,
       B, i, key, off, events, n_events);
 }
 
+// MT: stock-seed mode -- RandomBot's moves from the game's CPython stream
+// (mt_policy_pair), the stream's index written back.
 #if ORX_HOST_TU
+template <bool MT>
 __global__ void __launch_bounds__(256) policy_kernel(orx_state_t st, int32_t pol1, int32_t pol2,
                                                      int8_t* __restrict__ actions, uint32_t B,
                                                      Key key, uint32_t off) {
@@ -3027,7 +3056,7 @@ __global__ void __launch_bounds__(256) policy_kernel(orx_state_t st, int32_t pol
     p1.sx = st.st_x[i]; p2.sx = st.st_x[B + i];
     p1.sy = st.st_y[i]; p2.sy = st.st_y[B + i];
   }
-  const bool need_rng = pol1 == ORX_POLICY_RANDOM || pol2 == ORX_POLICY_RANDOM;
+  const bool need_rng = !MT && (pol1 == ORX_POLICY_RANDOM || pol2 == ORX_POLICY_RANDOM);
   const uint32_t ep = need_rng ? (uint32_t)st.episode[i] : 0u;
   const int32_t tick = need_rng ? st.tick[i] : 0;
   uint16_t* out = reinterpret_cast<uint16_t*>(actions);
@@ -3037,8 +3066,16 @@ __global__ void __launch_bounds__(256) policy_kernel(orx_state_t st, int32_t pol
     a1 = (int8_t)(prev & 0xFF);
     a2 = (int8_t)(prev >> 8);
   }
-  const W4 tb = need_rng ? tick_block(key, off + i, ep, tick) : W4{0, 0, 0, 0};
-  policy_pair(key, off + i, ep, tick, pol1, pol2, tb, p1, p2, a1, a2);
+  if constexpr (MT) {
+    MtStream py;
+    py.open(st.mt_py, B, i);
+    bool err = false;
+    mt_policy_pair(py, pol1, pol2, p1, p2, a1, a2, err);
+    py.close();
+  } else {
+    const W4 tb = need_rng ? tick_block(key, off + i, ep, tick) : W4{0, 0, 0, 0};
+    policy_pair(key, off + i, ep, tick, pol1, pol2, tb, p1, p2, a1, a2);
+  }
   out[i] = pack_actions(a1, a2);
 }
 #endif  // ORX_HOST_TU
@@ -3813,6 +3850,29 @@ struct TrajWriter {
   }
 };
 
+// Stages the bank's tiles in LDS: the whole block, before any thread exits.
+// n: the bank's bytes, or 0: not staged (too large, or disabled).
+template <bool GRID>
+__device__ __forceinline__ bool stage_tiles(const orx_state_t& st, uint32_t n) {
+  if constexpr (GRID) {
+    if (n > 0u) {
+      const uint8_t* src = st.bank_tiles;
+      for (uint32_t k = threadIdx.x * 4u; k < n; k += blockDim.x * 4u) {
+        if (k + 4u <= n) {
+          uint32_t v;
+          __builtin_memcpy(&v, src + k, 4);
+          __builtin_memcpy(orx_lds_tiles + k, &v, 4);
+        } else {
+          for (uint32_t j = k; j < n; ++j) orx_lds_tiles[j] = src[j];
+        }
+      }
+      __syncthreads();
+      return true;
+    }
+  }
+  return false;
+}
+
 // PM (policy mode, compile-time): 0 generic; 1 both players RandomBot, obs
 // and act given, no extension flags (the headline C3/C2 form); 2 both
 // StaircaseBot, obs and act given, at most separation damage (C5); 3 both
@@ -3834,24 +3894,7 @@ __global__ void __launch_bounds__(kRolloutBlock) rollout_kernel(orx_cfg_t hc, or
                        : PM == 2 ? (int32_t)ORX_POLICY_STAIRCASE : pol1_;
   const int32_t pol2 = (PM == 1 || PM == 3) ? (int32_t)ORX_POLICY_RANDOM
                        : PM == 2 ? (int32_t)ORX_POLICY_STAIRCASE : pol2_;
-  bool lds_tiles = false;
-  if constexpr (GRID) {  // stage the bank's tiles in LDS (the whole block, before any exit)
-    const uint32_t n = lds_n;  // the bank's bytes, or 0: not staged (too large, or disabled)
-    if (n > 0u) {
-      const uint8_t* src = st.bank_tiles;
-      for (uint32_t k = threadIdx.x * 4u; k < n; k += blockDim.x * 4u) {
-        if (k + 4u <= n) {
-          uint32_t v;
-          __builtin_memcpy(&v, src + k, 4);
-          __builtin_memcpy(orx_lds_tiles + k, &v, 4);
-        } else {
-          for (uint32_t j = k; j < n; ++j) orx_lds_tiles[j] = src[j];
-        }
-      }
-      __syncthreads();
-      lds_tiles = true;
-    }
-  }
+  const bool lds_tiles = stage_tiles<GRID>(st, lds_n);
   uint32_t i = xcd_block() * blockDim.x + threadIdx.x;
   if (lanes < 64u) {  // uniform: lanes >= `lanes` of every wave idle
     if ((threadIdx.x & 63u) >= lanes) return;
@@ -4142,23 +4185,7 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
                                                                      uint32_t B, Key key,
                                                                      uint32_t off, uint32_t lanes,
                                                                      uint32_t lds_n) {
-  bool lds_tiles = false;
-  if constexpr (GRID) {  // stage the bank's tiles in LDS (the whole block, before any exit)
-    if (lds_n > 0u) {
-      const uint8_t* src = st.bank_tiles;
-      for (uint32_t k = threadIdx.x * 4u; k < lds_n; k += blockDim.x * 4u) {
-        if (k + 4u <= lds_n) {
-          uint32_t v;
-          __builtin_memcpy(&v, src + k, 4);
-          __builtin_memcpy(orx_lds_tiles + k, &v, 4);
-        } else {
-          for (uint32_t j = k; j < lds_n; ++j) orx_lds_tiles[j] = src[j];
-        }
-      }
-      __syncthreads();
-      lds_tiles = true;
-    }
-  }
+  const bool lds_tiles = stage_tiles<GRID>(st, lds_n);
   const uint32_t lane = threadIdx.x & 63u;
   if (lane >= 2u * lanes) return;  // uniform per wave
   const uint32_t i = ((xcd_block() * blockDim.x + threadIdx.x) >> 6) * lanes + (lane >> 1);
@@ -4962,18 +4989,6 @@ __global__ void __launch_bounds__(256) mt_seed_kernel(orx_state_t st, uint32_t B
 }
 #endif  // ORX_HOST_TU
 
-// RandomBot.move = random.choice(list(Move)) = Move(1 + _randbelow(5))
-// (randombot.py:21) from the game's CPython stream; StaircaseBot as usual.
-__device__ __forceinline__ void mt_policy_pair(MtStream& py, int32_t pol1, int32_t pol2,
-                                               const Player& p1, const Player& p2, int32_t& a1,
-                                               int32_t& a2, bool& err) {
-  int32_t r[2] = {ORX_MOVE_STAY, ORX_MOVE_STAY};
-  int nr = 0;
-  if (pol1 == ORX_POLICY_RANDOM) r[nr++] = 1 + (int32_t)py_randbelow(py, Key{0, 0}, 5u, err);
-  if (pol2 == ORX_POLICY_RANDOM) r[nr++] = 1 + (int32_t)py_randbelow(py, Key{0, 0}, 5u, err);
-  assign_moves(pol1, pol2, r[0], r[1], p1, p2, a1, a2);
-}
-
 // random.shuffle of the two players (updater.py:114: player 1 first iff
 // _randbelow(2) == 1), then of the NPC updents (:127), whose order cannot
 // matter (they Stay) but whose draws advance the stream.
@@ -4985,63 +5000,6 @@ __device__ __forceinline__ bool mt_shuffles(MtStream& py, const Npcs<NCAP>& npc,
       py_randbelow(py, Key{0, 0}, (uint32_t)n + 1u, err);
   return p1_first;
 }
-
-template <int NCAP, bool GRID>
-__global__ void __launch_bounds__(256) mt_reset_kernel(orx_cfg_t hc, orx_state_t st,
-                                                       const uint8_t* __restrict__ mask,
-                                                       uint32_t B) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  if (mask && !mask[i]) return;
-  const Cfg c = make_cfg(hc, st);
-  MtSrc src;
-  src.open(st, c, B, i);
-  Player p1, p2;
-  Npcs<NCAP> npc;
-  npc.bind(st, c, B, i);
-  int32_t tick, status;
-  setup_game<NCAP, GRID>(c, Key{0, 0}, src, p1, p2, npc, tick, status);
-  src.close();
-  store_players<GRID>(st, B, i, p1, p2, true);
-  Items<NCAP> items;
-  items.clear();
-  store_rpg(st, c, B, i, p1, p2, npc, items);
-  st.tick[i] = tick;
-  st.status[i] = status;
-  if (c.ext & ORX_EXT_SEPARATION_DAMAGE) st.sep_start[i] = -1;
-  if constexpr (NCAP > 0) {
-    npc.store_alive(st.npc_alive, B, i);
-    store_new_npcs(st, c, B, i, npc);
-  }
-}
-
-#if ORX_HOST_TU
-__global__ void __launch_bounds__(256) mt_policy_kernel(orx_state_t st, int32_t pol1,
-                                                        int32_t pol2,
-                                                        int8_t* __restrict__ actions,
-                                                        uint32_t B) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  Player p1, p2;
-  p1.x = st.p_x[i]; p2.x = st.p_x[B + i];
-  p1.y = st.p_y[i]; p2.y = st.p_y[B + i];
-  p1.sx = st.st_x[i]; p2.sx = st.st_x[B + i];
-  p1.sy = st.st_y[i]; p2.sy = st.st_y[B + i];
-  uint16_t* out = reinterpret_cast<uint16_t*>(actions);
-  int32_t a1 = ORX_MOVE_STAY, a2 = ORX_MOVE_STAY;
-  if (pol1 == ORX_POLICY_NONE || pol2 == ORX_POLICY_NONE) {
-    const uint16_t prev = out[i];
-    a1 = (int8_t)(prev & 0xFF);
-    a2 = (int8_t)(prev >> 8);
-  }
-  MtStream py;
-  py.open(st.mt_py, B, i);
-  bool err = false;
-  mt_policy_pair(py, pol1, pol2, p1, p2, a1, a2, err);
-  py.close();
-  out[i] = pack_actions(a1, a2);
-}
-#endif  // ORX_HOST_TU
 
 template <int NCAP, bool EV, bool GRID, bool MOV = false>
 __global__ void __launch_bounds__(256) mt_step_kernel(orx_cfg_t hc, orx_state_t st,
@@ -5490,7 +5448,7 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
 // X-macro lists shared by the host dispatch (below) and the split build's
 // explicit instantiations, so the two cannot drift apart.
 // ---------------------------------------------------------------------------
-// (NCAP, GRID): reset_kernel, mt_reset_kernel, mt_rollout_kernel, step_n_kernel
+// (NCAP, GRID): reset_kernel (both random sources), mt_rollout_kernel, step_n_kernel
 #define ORX_NG_LIST(X)                                                                          \
   X(0, false) X(8, false) X(16, false) X(kDense, false)                                         \
   X(0, true) X(8, true) X(16, true) X(kDense, true)
@@ -5583,12 +5541,11 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
 #else
 #define ORX_INST
 #endif
-#define ORX_I_RESET(N, G)                                                                       \
-  ORX_INST template __global__ void reset_kernel<N, G>(orx_cfg_t, orx_state_t, const uint8_t*,  \
-                                                       uint32_t, Key, uint32_t);
-#define ORX_I_MT_RESET(N, G)                                                                    \
-  ORX_INST template __global__ void mt_reset_kernel<N, G>(orx_cfg_t, orx_state_t,               \
-                                                          const uint8_t*, uint32_t);
+#define ORX_I_RESET_MT(N, G, MT)                                                                \
+  ORX_INST template __global__ void reset_kernel<N, G, MT>(orx_cfg_t, orx_state_t,              \
+                                                           const uint8_t*, uint32_t, Key,       \
+                                                           uint32_t);
+#define ORX_I_RESET(N, G) ORX_I_RESET_MT(N, G, false) ORX_I_RESET_MT(N, G, true)
 #define ORX_I_MT_ROLLOUT(N, G)                                                                  \
   ORX_INST template __global__ void mt_rollout_kernel<N, G>(orx_cfg_t, orx_state_t, int32_t,    \
                                                             int32_t, int32_t, int32_t*, int8_t*, \
@@ -5704,7 +5661,6 @@ ORX_MOV_ROLLOUT_LIST(ORX_I_MOV_ROLLOUT)
 #endif
 #if ORX_OWNS(12)
 ORX_NG_LIST(ORX_I_RESET)
-ORX_NG_LIST(ORX_I_MT_RESET)
 ORX_NG_LIST(ORX_I_MT_ROLLOUT)
 ORX_NG_LIST(ORX_I_STEP_N)
 ORX_REPLAY_LIST(ORX_I_REPLAY)
@@ -6007,8 +5963,8 @@ int orx_reset(const orx_cfg_t* cfg, const orx_state_t* st, const uint8_t* mask, 
   const bool mt = cfg->rng == ORX_RNG_MT19937;
 #define ORX_RESET(N, G)                                                                         \
   if (nc == N && grid == G)                                                                     \
-    return mt ? launch("orx_reset", mt_reset_kernel<N, G>, B, s, *cfg, *st, mask, B)            \
-              : launch("orx_reset", reset_kernel<N, G>, B, s, *cfg, *st, mask, B, k, off);
+    return launch("orx_reset", mt ? reset_kernel<N, G, true> : reset_kernel<N, G, false>, B, s, \
+                  *cfg, *st, mask, B, k, off);
   ORX_NG_LIST(ORX_RESET)
 #undef ORX_RESET
   return fail(ORX_EIO, "orx_reset: no kernel instance for this configuration");
@@ -6148,11 +6104,9 @@ int orx_policy(const orx_cfg_t* cfg, const orx_state_t* st, int32_t policy_p1, i
   if ((r = check_state(cfg, st, false))) return r;
   if (!actions) return fail(ORX_EINVAL, "actions is NULL");
   const uint32_t B = (uint32_t)n_games, off = (uint32_t)game_offset;
-  if (cfg->rng == ORX_RNG_MT19937)
-    return launch("orx_policy", mt_policy_kernel, B, (hipStream_t)stream, *st, policy_p1,
-                  policy_p2, actions, B);
-  return launch("orx_policy", policy_kernel, B, (hipStream_t)stream, *st, policy_p1, policy_p2,
-                actions, B, make_key(seed), off);
+  const bool mt = cfg->rng == ORX_RNG_MT19937;
+  return launch("orx_policy", mt ? policy_kernel<true> : policy_kernel<false>, B,
+                (hipStream_t)stream, *st, policy_p1, policy_p2, actions, B, make_key(seed), off);
 }
 
 int orx_env_step(const orx_cfg_t* cfg, const orx_state_t* st, const void* actions,

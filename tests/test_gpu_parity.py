@@ -1421,3 +1421,78 @@ def test_step_n_equals_step(name):
         c_obs = torch.zeros((T, 6, B), dtype=torch.int32, device=eng.device)
         eng2.step_n(a, obs=c_obs, obs_format=OBS_COMPACT)
         assert np.array_equal(decode_compact(c_obs).cpu().numpy(), o), name
+
+
+# stock-seed mode (rng=1): the fused rollout against policy + step, and what a
+# refused pair leaves alone.  257 games: one full 256-thread workgroup and a
+# one-lane tail.
+_STOCK_REG = dict(width=10, height=9, n_npcs=4, despawn=2, max_ticks=30, rng=1)
+STOCK_CASES = {
+    "register": _STOCK_REG,
+    "dense": dict(_STOCK_REG, n_npcs=20),
+    "bank": ORACLE_CASES["stock_bank_separated"][0],
+    "moving": dict(width=8, height=8, n_npcs=6, max_ticks=30, npc_policy=1, rng=1),
+}
+
+
+def _stock_obs_rows(e):
+    import torch
+    p = [t[k] for k in (0, 1) for t in (e.p_x, e.p_y, e.p_depth, e.p_health)]
+    return torch.stack(p + [e.tick, e.status, e.st_x[0], e.st_y[0], e.st_x[1], e.st_y[1]])
+
+
+@pytest.mark.parametrize("autoreset", [1, 0])
+@pytest.mark.parametrize("name", sorted(STOCK_CASES))
+def test_stock_rollout_equals_policy_step(name, autoreset):
+    """Stock-seed mode: rollout(64, 1, 2) in one launch leaves every array of
+    the snapshot (the games' MT19937 streams and dungeon stores included) and
+    every trajectory row as 64 x step(policy(1, 2)) does."""
+    import torch
+    from optimax_rogue_amd.enums import OBS_FIELDS
+    cfg = dict(STOCK_CASES[name], autoreset=autoreset)
+    lay = _bank(*ORACLE_BANKS["stock_bank_separated"]) if name == "bank" else None
+    B, T, seed = 257, 64, 31
+    roll = _engine(cfg, B, seed, layouts=lay)
+    step = _engine(cfg, B, seed, layouts=lay)
+    obs = torch.zeros((T, len(OBS_FIELDS), B), dtype=torch.int32, device=roll.device)
+    act = torch.zeros((T, B, 2), dtype=torch.int8, device=roll.device)
+    roll.rollout(T, 1, 2, obs=obs, act=act)
+    want_obs, want_act = [], []
+    for _ in range(T):
+        want_act.append(step.policy(1, 2).clone())
+        step.step()
+        want_obs.append(_stock_obs_rows(step))
+    assert torch.equal(act, torch.stack(want_act)), f"{name} action rows"
+    assert torch.equal(obs, torch.stack(want_obs)), f"{name} observation rows"
+    got, want = roll.snapshot(), step.snapshot()
+    assert sorted(got) == sorted(want) and {"mt_py", "mt_np", "dstore"} <= set(got)
+    for k, w in want.items():
+        assert np.array_equal(got[k], w), f"{name} autoreset={autoreset}: {k}"
+    if autoreset:
+        assert (want["episode"] >= 1).all() or name == "bank"   # (max_ticks 200 there)
+
+
+def test_stock_refusals_leave_streams():
+    """Stock-seed mode: one step in which every odd game's pair holds an
+    illegal move.  Those games stop with BAD_ACTION and nothing else of theirs
+    changes -- not their streams (mt_py, mt_np) nor their dungeon store; the
+    even games step as in an engine that was given the same legal pairs."""
+    from optimax_rogue_amd.enums import STATUS_BAD_ACTION
+    B, seed = 257, 32
+    eng = _engine(_STOCK_REG, B, seed)
+    ref = _engine(_STOCK_REG, B, seed)
+    legal = ref.policy(1, 2).clone()
+    eng.policy(1, 2)                      # (the same draws: the same streams)
+    before = eng.snapshot()
+    a = legal.clone()
+    a[1::2, 0] = 9
+    eng.step(a)
+    ref.step(legal)
+    got, want = eng.snapshot(), ref.snapshot()
+    odd = np.arange(B) % 2 == 1
+    assert {"mt_py", "mt_np", "dstore"} <= set(got)
+    assert (got["status"][odd] == STATUS_BAD_ACTION).all()
+    for k, w in want.items():
+        assert np.array_equal(got[k][..., ~odd], w[..., ~odd]), k
+        if k != "status":
+            assert np.array_equal(got[k][..., odd], before[k][..., odd]), k
