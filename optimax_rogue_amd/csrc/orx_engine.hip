@@ -943,6 +943,7 @@ struct PhiloxSrc {
   }
   __device__ __forceinline__ void open(const orx_state_t&, const Cfg&, uint32_t, uint32_t) {}
   __device__ __forceinline__ void close() const {}
+  __device__ __forceinline__ void episode(uint32_t e) { ep = e; }  // the game's next episode
   __device__ __forceinline__ Stream init() const {
     Stream s;
     s.init(game, ep, 0, tag(PUR_INIT, 0));
@@ -986,6 +987,7 @@ struct MtSrc {
     return 2 * k * B;
   }
   __device__ __forceinline__ void close() const { py.close(); np.close(); }
+  __device__ __forceinline__ void episode(uint32_t) {}  // (the streams run on)
   __device__ __forceinline__ MtStream& init() { return np; }
   __device__ __forceinline__ MtStream& spawn(int32_t) { return np; }
   template <bool GRID>
@@ -1390,6 +1392,18 @@ __device__ __forceinline__ bool first_from_packed(uint32_t pk, Key key, uint32_t
 __device__ __forceinline__ bool p1_first_draw(Key key, uint32_t game, uint32_t ep, int32_t tick,
                                               bool& err) {
   return first_from_packed(tick_block(key, game, ep, tick).a, key, game, ep, tick, err);
+}
+
+// random.shuffle of the two players (updater.py:114: player 1 first iff
+// _randbelow(2) == 1), then of the NPC updents (:127), whose order cannot
+// matter (they Stay) but whose draws advance the stream.
+template <int NCAP>
+__device__ __forceinline__ bool mt_shuffles(MtStream& py, const Npcs<NCAP>& npc, bool& err) {
+  const bool p1_first = py_randbelow(py, Key{0, 0}, 2u, err) == 1u;
+  if constexpr (NCAP > 0)
+    for (int32_t n = npc.count_alive() - 1; n >= 1; --n)
+      py_randbelow(py, Key{0, 0}, (uint32_t)n + 1u, err);
+  return p1_first;
 }
 
 // RandomBot / StaircaseBot moves for both players (policy codes ORX_POLICY_*)
@@ -2925,7 +2939,7 @@ struct NoOut {
   __device__ __forceinline__ void operator()(const Player&, const Player&, int32_t, int32_t) {}
 };
 
-template <int NCAP, bool EV, bool GRID, bool EXT, bool MOV, class A, class O = NoOut>
+template <int NCAP, bool EV, bool GRID, bool EXT, bool MOV, class Src, class A, class O = NoOut>
 __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t& st, A get_action,
                                           uint32_t B, uint32_t i, Key key, uint32_t off,
                                           int32_t* __restrict__ events,
@@ -2948,10 +2962,12 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
   Items<NCAP> items;
   int32_t sep = -1;
   W4 tb0{0, 0, 0, 0};  // (kOut) the tick block: player 2's policy and the initiative draw
+  Src src = Src::make(key, game, 0u);
   if constexpr (kEager) {
     load_players<GRID>(st, B, i, p1, p2);
     tick = st.tick[i];
     ep = (uint32_t)st.episode[i];
+    src.open(st, c, B, i);  // (stock-seed mode: the streams' indices with the state words)
     load_npcs(st, c, B, i, npc);
     load_rpg(st, c, B, i, p1, p2, npc, items);
     if (c.ext & ORX_EXT_SEPARATION_DAMAGE) sep = st.sep_start[i];
@@ -2965,7 +2981,10 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
       return;
     }
     const uint32_t ep1 = (kEager ? ep : (uint32_t)st.episode[i]) + 1u;
-    setup_game<NCAP, GRID>(c, key, game, ep1, p1, p2, npc, tick, status);
+    if constexpr (!kEager) src.open(st, c, B, i);
+    src.episode(ep1);
+    setup_game<NCAP, GRID>(c, key, src, p1, p2, npc, tick, status);
+    src.close();  // (stock-seed mode: the streams' indices, before the state)
     store_players<GRID>(st, B, i, p1, p2, true);
     items.clear();
     store_rpg(st, c, B, i, p1, p2, npc, items);
@@ -2996,23 +3015,27 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
     load_npcs(st, c, B, i, npc);
     load_rpg(st, c, B, i, p1, p2, npc, items);
     if (c.ext & ORX_EXT_SEPARATION_DAMAGE) sep = st.sep_start[i];
+    src.open(st, c, B, i);
   }
+  src.episode(ep);
   NpcMem m{st.npc_pos, st.npc_health, B, i};
   Deltas dl = {0, 0, 0, 0, 0, 0};
   const int32_t ev_cap = MOV ? max_events_for(c.npc_pol, c.K) : ORX_MAX_EVENTS;
   Events<EV> ev{EV ? events + (size_t)i * (size_t)ev_cap * 4 : nullptr, 0, ev_cap};
   bool err = false;
   if constexpr (MOV) {  // moving NPCs: the literal ordered tick draws its own shuffles
-    PhiloxSrc src{key, game, ep};
     tick_moving<NCAP, EV, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err, dl, ev,
                                 sep);
     store_npc_cells(st, c, B, i, npc);
   } else {
-    const bool p1_first = kOut ? first_from_packed(tb0.a, key, game, ep, tick, err)
-                               : p1_first_draw(key, game, ep, tick, err);
-    tick_game<NCAP, EV, GRID>(c, key, game, ep, p1_first, p1, p2, npc, items, m, tick, status,
-                              err, dl, ev, sep);
+    bool p1_first;  // the initiative (stock-seed mode: and the NPC shuffles' draws)
+    if constexpr (Src::kMt) p1_first = mt_shuffles(src.py, npc, err);
+    else p1_first = kOut ? first_from_packed(tb0.a, key, game, ep, tick, err)
+                         : p1_first_draw(key, game, ep, tick, err);
+    tick_game<NCAP, EV, GRID>(c, key, src, game, ep, p1_first, p1, p2, npc, items, m, tick,
+                              status, err, dl, ev, sep);
   }
+  src.close();
   if (c.ext & ORX_EXT_SEPARATION_DAMAGE) st.sep_start[i] = sep;
   store_rpg(st, c, B, i, p1, p2, npc, items);
   store_players_tick<GRID>(st, B, i, p1, p2, dl.descend != 0, EXT ? true : dl.combat != 0);
@@ -3024,7 +3047,9 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
   out(p1, p2, tick, status);
 }
 
-template <int NCAP, bool EV, bool GRID, bool EXT = true, bool MOV = false>
+// MT: stock-seed mode -- the tick's draws from the game's own streams, which a
+// refused pair or a finished game without autoreset leaves as they are
+template <int NCAP, bool EV, bool GRID, bool EXT = true, bool MOV = false, bool MT = false>
 __global__ void __launch_bounds__(256) step_kernel(orx_cfg_t hc, orx_state_t st,
                                                    const int8_t* __restrict__ actions, uint32_t B,
                                                    Key key, uint32_t off,
@@ -3032,7 +3057,7 @@ __global__ void __launch_bounds__(256) step_kernel(orx_cfg_t hc, orx_state_t st,
                                                    int32_t* __restrict__ n_events) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  step_game<NCAP, EV, GRID, EXT, MOV>(
+  step_game<NCAP, EV, GRID, EXT, MOV, std::conditional_t<MT, MtSrc, PhiloxSrc>>(
       hc, st,
       [&](const Player&, const Player&, int32_t, uint32_t, const W4&) {
         return reinterpret_cast<const uint16_t*>(actions)[i];
@@ -3173,8 +3198,8 @@ env_step_kernel(
       pair = pack_actions(l1, l2);
       out(p1, p2, st.tick[i], before);
     } else {
-      step_game<NCAP, false, GRID, EXT, MOV>(hc, st, get_action, B, i, key, off, nullptr,
-                                             nullptr, out);
+      step_game<NCAP, false, GRID, EXT, MOV, PhiloxSrc>(hc, st, get_action, B, i, key, off,
+                                                        nullptr, nullptr, out);
     }
     reinterpret_cast<uint16_t*>(act)[i] = pair;
   }
@@ -4989,159 +5014,6 @@ __global__ void __launch_bounds__(256) mt_seed_kernel(orx_state_t st, uint32_t B
 }
 #endif  // ORX_HOST_TU
 
-// random.shuffle of the two players (updater.py:114: player 1 first iff
-// _randbelow(2) == 1), then of the NPC updents (:127), whose order cannot
-// matter (they Stay) but whose draws advance the stream.
-template <int NCAP>
-__device__ __forceinline__ bool mt_shuffles(MtStream& py, const Npcs<NCAP>& npc, bool& err) {
-  const bool p1_first = py_randbelow(py, Key{0, 0}, 2u, err) == 1u;
-  if constexpr (NCAP > 0)
-    for (int32_t n = npc.count_alive() - 1; n >= 1; --n)
-      py_randbelow(py, Key{0, 0}, (uint32_t)n + 1u, err);
-  return p1_first;
-}
-
-template <int NCAP, bool EV, bool GRID, bool MOV = false>
-__global__ void __launch_bounds__(256) mt_step_kernel(orx_cfg_t hc, orx_state_t st,
-                                                      const int8_t* __restrict__ actions,
-                                                      uint32_t B, Key key, uint32_t off,
-                                                      int32_t* __restrict__ events,
-                                                      int32_t* __restrict__ n_events) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  const Cfg c = make_cfg(hc, st);
-  const uint32_t game = off + i;
-  int32_t status = st.status[i];
-  Npcs<NCAP> npc;
-  npc.bind(st, c, B, i);
-  Player p1, p2;
-  if (status != ORX_IN_PROGRESS) {
-    if (EV) n_events[i] = 0;
-    if (!c.autoreset) return;
-    MtSrc src;
-    src.open(st, c, B, i);
-    const uint32_t ep = (uint32_t)st.episode[i] + 1u;
-    int32_t tick;
-    setup_game<NCAP, GRID>(c, key, src, p1, p2, npc, tick, status);
-    src.close();
-    store_players<GRID>(st, B, i, p1, p2, true);
-    Items<NCAP> items;
-    items.clear();
-    store_rpg(st, c, B, i, p1, p2, npc, items);
-    st.tick[i] = tick;
-    st.status[i] = status;
-    st.episode[i] = (int32_t)ep;
-    if (c.ext & ORX_EXT_SEPARATION_DAMAGE) st.sep_start[i] = -1;
-    if constexpr (NCAP > 0) {
-      npc.store_alive(st.npc_alive, B, i);
-      store_new_npcs(st, c, B, i, npc);
-    }
-    return;
-  }
-  const uint16_t a = reinterpret_cast<const uint16_t*>(actions)[i];
-  p1.move = (int8_t)(a & 0xFF);
-  p2.move = (int8_t)(a >> 8);
-  if (!valid_move(c, p1.move) || !valid_move(c, p2.move)) {
-    st.status[i] = ORX_STATUS_BAD_ACTION;
-    if (EV) n_events[i] = 0;
-    return;
-  }
-  const uint32_t ep = (uint32_t)st.episode[i];
-  int32_t tick = st.tick[i];
-  load_players<GRID>(st, B, i, p1, p2);
-  load_npcs(st, c, B, i, npc);
-  Items<NCAP> items;
-  load_rpg(st, c, B, i, p1, p2, npc, items);
-  NpcMem m{st.npc_pos, st.npc_health, B, i};
-  Deltas dl = {0, 0, 0, 0, 0, 0};
-  const int32_t ev_cap = MOV ? max_events_for(c.npc_pol, c.K) : ORX_MAX_EVENTS;
-  Events<EV> ev{EV ? events + (size_t)i * (size_t)ev_cap * 4 : nullptr, 0, ev_cap};
-  bool err = false;
-  MtSrc src;
-  src.open(st, c, B, i);
-  int32_t sep = (c.ext & ORX_EXT_SEPARATION_DAMAGE) ? st.sep_start[i] : -1;
-  if constexpr (MOV) {
-    tick_moving<NCAP, EV, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err, dl, ev,
-                                sep);
-    store_npc_cells(st, c, B, i, npc);
-  } else {
-    const bool p1_first = mt_shuffles(src.py, npc, err);
-    tick_game<NCAP, EV, GRID>(c, key, src, game, ep, p1_first, p1, p2, npc, items, m, tick,
-                              status, err, dl, ev, sep);
-  }
-  src.close();
-  store_rpg(st, c, B, i, p1, p2, npc, items);
-  if (c.ext & ORX_EXT_SEPARATION_DAMAGE) st.sep_start[i] = sep;
-  store_players<GRID>(st, B, i, p1, p2, dl.descend != 0);
-  st.tick[i] = tick;
-  st.status[i] = status;
-  if (NCAP > 0 && dl.npc_death) npc.store_alive(st.npc_alive, B, i);
-  flush_deltas(st, B, i, dl);
-  if (EV) n_events[i] = ev.n;
-}
-
-template <int NCAP, bool GRID>
-__global__ void __launch_bounds__(256) mt_rollout_kernel(orx_cfg_t hc, orx_state_t st,
-                                                         int32_t pol1, int32_t pol2,
-                                                         int32_t n_ticks,
-                                                         int32_t* __restrict__ obs,
-                                                         int8_t* __restrict__ act, uint32_t B,
-                                                         Key key, uint32_t off, int32_t fmt) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  const Cfg c = make_cfg(hc, st);
-  const uint32_t game = off + i;
-  Player p1, p2;
-  load_players<GRID>(st, B, i, p1, p2);
-  int32_t tick = st.tick[i];
-  int32_t status = st.status[i];
-  uint32_t ep = (uint32_t)st.episode[i];
-  Npcs<NCAP> npc;
-  npc.bind(st, c, B, i);
-  load_npcs(st, c, B, i, npc);
-  NpcMem m{st.npc_pos, st.npc_health, B, i};
-  Items<NCAP> items;
-  load_rpg(st, c, B, i, p1, p2, npc, items);
-  Deltas dl = {0, 0, 0, 0, 0, 0};
-  int32_t sep = (c.ext & ORX_EXT_SEPARATION_DAMAGE) ? st.sep_start[i] : -1;
-  bool stairs_dirty = false, npc_dirty = false;
-  MtSrc src;
-  src.open(st, c, B, i);
-  TrajWriter<false> traj(obs, act, B, i, fmt);
-  for (int32_t t = 0; t < n_ticks; ++t) {
-    int32_t a1 = ORX_MOVE_STAY, a2 = ORX_MOVE_STAY;
-    bool err = false;
-    mt_policy_pair(src.py, pol1, pol2, p1, p2, a1, a2, err);
-    if (status == ORX_IN_PROGRESS) {
-      p1.move = a1; p2.move = a2;
-      const int32_t descents = dl.descend;
-      const bool p1_first = mt_shuffles(src.py, npc, err);
-      Events<false> ev{nullptr, 0};
-      tick_game<NCAP, false, GRID>(c, key, src, game, ep, p1_first, p1, p2, npc, items, m, tick,
-                                   status, err, dl, ev, sep);
-      stairs_dirty |= dl.descend != descents;
-    } else if (c.autoreset) {
-      ep += 1;
-      setup_game<NCAP, GRID>(c, key, src, p1, p2, npc, tick, status);
-      items.clear();
-      if constexpr (NCAP > 0) store_new_npcs(st, c, B, i, npc);
-      stairs_dirty = true;
-      npc_dirty = true;
-      sep = -1;
-    }
-    traj.write(t, p1, p2, tick, status, a1, a2);
-  }
-  src.close();
-  store_players<GRID>(st, B, i, p1, p2, stairs_dirty);
-  store_rpg(st, c, B, i, p1, p2, npc, items);
-  st.tick[i] = tick;
-  st.status[i] = status;
-  st.episode[i] = (int32_t)ep;
-  if (c.ext & ORX_EXT_SEPARATION_DAMAGE) st.sep_start[i] = sep;
-  if (NCAP > 0 && (npc_dirty || dl.npc_death)) npc.store_alive(st.npc_alive, B, i);
-  flush_deltas(st, B, i, dl);
-}
-
 // orx_step_n: n_ticks x orx_step with given actions (actions[t][b] = the
 // pair of tick t, player 1 in the low byte) in one launch, the state in
 // registers between ticks -- the multi-tick Updater.update loop of a replay
@@ -5255,19 +5127,22 @@ __global__ void __launch_bounds__(256) step_n_kernel(orx_cfg_t hc, orx_state_t s
     step_n_game<NCAP, GRID, 1, MOV>(hc, st, actions, n_ticks, obs, B, i, key, off);
 }
 
-// orx_rollout with moving NPCs (cfg.npc_policy): n_ticks x (the bots' moves,
-// then the moving-NPC tick or the autoreset), one lane per game, each tick's
-// observation row (format fmt) and actions written when obs / act are given.
-// MT: stock-seed mode (the bots and the tick draw from the game's CPython
-// random in the reference's call order, as mt_rollout_kernel).
-template <int NCAP, bool GRID, bool MT>
-__global__ void __launch_bounds__(256) mov_rollout_kernel(orx_cfg_t hc, orx_state_t st,
-                                                          int32_t pol1, int32_t pol2,
-                                                          int32_t n_ticks,
-                                                          int32_t* __restrict__ obs,
-                                                          int8_t* __restrict__ act, uint32_t B,
-                                                          Key key, uint32_t off, int32_t fmt,
-                                                          uint32_t lanes) {
+// orx_rollout, one lane per game, for stock-seed mode and for moving NPCs
+// (cfg.npc_policy): n_ticks x (the bots' moves, then the tick or the
+// autoreset), each tick's observation row (format fmt) and actions written
+// when obs / act are given.  MT: stock-seed mode (the bots and the tick draw
+// from the game's CPython random in the reference's call order).  MOV: the
+// moving-NPC tick, else tick_game behind mt_shuffles.  (No <false, false>
+// instance: the keyed generic rollout is rollout_kernel's PM 0.)
+template <int NCAP, bool GRID, bool MT, bool MOV>
+__global__ void __launch_bounds__(256) lane_rollout_kernel(orx_cfg_t hc, orx_state_t st,
+                                                           int32_t pol1, int32_t pol2,
+                                                           int32_t n_ticks,
+                                                           int32_t* __restrict__ obs,
+                                                           int8_t* __restrict__ act, uint32_t B,
+                                                           Key key, uint32_t off, int32_t fmt,
+                                                           uint32_t lanes) {
+  static_assert(MT || MOV, "the keyed generic rollout is rollout_kernel<N, 0, ...>");
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (lanes < 64u) {  // uniform: lanes >= `lanes` of every wave idle (as rollout_kernel)
     if ((threadIdx.x & 63u) >= lanes) return;
@@ -5284,9 +5159,9 @@ __global__ void __launch_bounds__(256) mov_rollout_kernel(orx_cfg_t hc, orx_stat
   Npcs<NCAP> npc;
   npc.bind(st, c, B, i);
   load_npcs(st, c, B, i, npc);
-  // register NPCs keep their health in registers for the launch (as the
-  // rollout's NpcHpRegs), stored once at the end; dense NPCs' stays in HBM
-  constexpr bool kRegHp = NCAP > 0 && NCAP != kDense;
+  // moving register NPCs keep their health in registers for the launch (as the
+  // rollout's NpcHpRegs), stored once at the end; otherwise it stays in HBM
+  constexpr bool kRegHp = MOV && NCAP > 0 && NCAP != kDense;
   std::conditional_t<kRegHp, NpcHpRegs<NCAP>, NpcMem> m;
   if constexpr (kRegHp) m.load(st.npc_health, c.K, B, i);
   else m = NpcMem{st.npc_pos, st.npc_health, B, i};
@@ -5295,9 +5170,9 @@ __global__ void __launch_bounds__(256) mov_rollout_kernel(orx_cfg_t hc, orx_stat
   Deltas dl = {0, 0, 0, 0, 0, 0};
   int32_t sep = (c.ext & ORX_EXT_SEPARATION_DAMAGE) ? st.sep_start[i] : -1;
   bool stairs_dirty = false, npc_dirty = false;
-  std::conditional_t<MT, MtSrc, PhiloxSrc> src;
-  if constexpr (MT) src.open(st, c, B, i);
-  else src = PhiloxSrc{key, game, ep};
+  using Src = std::conditional_t<MT, MtSrc, PhiloxSrc>;
+  Src src = Src::make(key, game, ep);
+  src.open(st, c, B, i);
   TrajWriter<false> traj(obs, act, B, i, fmt);
   ORX_MCYC_BEGIN(cyl);
   for (int32_t t = 0; t < n_ticks; ++t) {
@@ -5319,16 +5194,23 @@ __global__ void __launch_bounds__(256) mov_rollout_kernel(orx_cfg_t hc, orx_stat
       p2.move = a2;
       const int32_t descents = dl.descend;
       Events<false> ev{nullptr, 0};
-      tick_moving<NCAP, false, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err, dl,
-                                     ev, sep, MT ? nullptr : &tb);
+      if constexpr (MOV) {
+        tick_moving<NCAP, false, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err,
+                                       dl, ev, sep, MT ? nullptr : &tb);
+        npc_dirty = true;
+      } else {
+        const bool p1_first = mt_shuffles(src.py, npc, err);
+        tick_game<NCAP, false, GRID>(c, key, src, game, ep, p1_first, p1, p2, npc, items, m, tick,
+                                     status, err, dl, ev, sep);
+      }
       stairs_dirty |= dl.descend != descents;
-      npc_dirty = true;
       ORX_MCYC_END(10, cyt);
     } else if (c.autoreset) {
       ORX_MCYC_BEGIN(cy7);
       ep += 1;
-      if constexpr (!MT) src.ep = ep;
+      src.episode(ep);
       setup_game<NCAP, GRID>(c, key, src, p1, p2, npc, tick, status);
+      items.clear();
       if constexpr (kRegHp) m.fill(c.npc_hp);  // (the cells: store_npc_cells at the end)
       else if constexpr (NCAP > 0) store_new_npcs(st, c, B, i, npc);
       stairs_dirty = true;
@@ -5341,14 +5223,16 @@ __global__ void __launch_bounds__(256) mov_rollout_kernel(orx_cfg_t hc, orx_stat
     ORX_MCYC_END(8, cy8);
   }
   ORX_MCYC_END(9, cyl);
-  if constexpr (MT) src.close();
+  src.close();
   store_players<GRID>(st, B, i, p1, p2, stairs_dirty);
+  // (no character mechanics with moving NPCs: check_cfg)
+  if constexpr (!MOV) store_rpg(st, c, B, i, p1, p2, npc, items);
   st.tick[i] = tick;
   st.status[i] = status;
   st.episode[i] = (int32_t)ep;
   if (c.ext & ORX_EXT_SEPARATION_DAMAGE) st.sep_start[i] = sep;
-  if (NCAP > 0 && npc_dirty) {
-    npc.store_alive(st.npc_alive, B, i);
+  if (NCAP > 0 && (npc_dirty || dl.npc_death)) npc.store_alive(st.npc_alive, B, i);
+  if (MOV && NCAP > 0 && npc_dirty) {
     store_npc_cells(st, c, B, i, npc);
     if constexpr (kRegHp) m.store(st.npc_health, c.K, B, i);
   }
@@ -5448,11 +5332,12 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
 // X-macro lists shared by the host dispatch (below) and the split build's
 // explicit instantiations, so the two cannot drift apart.
 // ---------------------------------------------------------------------------
-// (NCAP, GRID): reset_kernel (both random sources), mt_rollout_kernel, step_n_kernel
+// (NCAP, GRID): reset_kernel (both random sources), step_n_kernel, and
+// lane_rollout_kernel<N, G, true, false> (the stock-seed rollout)
 #define ORX_NG_LIST(X)                                                                          \
   X(0, false) X(8, false) X(16, false) X(kDense, false)                                         \
   X(0, true) X(8, true) X(16, true) X(kDense, true)
-// (NCAP, EV, GRID): step_kernel (all rules) and mt_step_kernel
+// (NCAP, EV, GRID): step_kernel (all rules, both random sources)
 #define ORX_STEP_LIST(X)                                                                        \
   X(0, false, false) X(0, true, false) X(8, false, false) X(8, true, false)                     \
   X(16, false, false) X(16, true, false) X(0, false, true) X(0, true, true)                     \
@@ -5519,8 +5404,8 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
 
 // moving NPCs (cfg.npc_policy != ORX_NPC_STAY): (NCAP, GRID) of
 // step_n_kernel<N, G, true> and env_step_kernel<N, G, true, true>, (NCAP, EV,
-// GRID) of step_kernel<N, E, G, true, true> and mt_step_kernel<N, E, G, true>,
-// (NCAP, GRID, MT) of mov_rollout_kernel
+// GRID) of step_kernel<N, E, G, true, true, MT> (both random sources),
+// (NCAP, GRID, MT) of lane_rollout_kernel<N, G, MT, true>
 #define ORX_MOV_NG_LIST(X)                                                                      \
   X(8, false) X(16, false) X(kDense, false) X(8, true) X(16, true) X(kDense, true)
 #define ORX_MOV_STEP_LIST(X)                                                                    \
@@ -5546,21 +5431,13 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
                                                            const uint8_t*, uint32_t, Key,       \
                                                            uint32_t);
 #define ORX_I_RESET(N, G) ORX_I_RESET_MT(N, G, false) ORX_I_RESET_MT(N, G, true)
-#define ORX_I_MT_ROLLOUT(N, G)                                                                  \
-  ORX_INST template __global__ void mt_rollout_kernel<N, G>(orx_cfg_t, orx_state_t, int32_t,    \
-                                                            int32_t, int32_t, int32_t*, int8_t*, \
-                                                            uint32_t, Key, uint32_t, int32_t);
-#define ORX_I_STEP(N, E, G)                                                                     \
-  ORX_INST template __global__ void step_kernel<N, E, G, true>(orx_cfg_t, orx_state_t,          \
-                                                               const int8_t*, uint32_t, Key,    \
-                                                               uint32_t, int32_t*, int32_t*);
+#define ORX_I_STEP_M(N, E, G, MOV, MT)                                                          \
+  ORX_INST template __global__ void step_kernel<N, E, G, true, MOV, MT>(                        \
+      orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*);
+#define ORX_I_STEP(N, E, G) ORX_I_STEP_M(N, E, G, false, false) ORX_I_STEP_M(N, E, G, false, true)
 #define ORX_I_STEP_REF(N)                                                                       \
   ORX_INST template __global__ void step_kernel<N, false, false, false>(                        \
       orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*);
-#define ORX_I_MT_STEP(N, E, G)                                                                  \
-  ORX_INST template __global__ void mt_step_kernel<N, E, G>(orx_cfg_t, orx_state_t,             \
-                                                            const int8_t*, uint32_t, Key,       \
-                                                            uint32_t, int32_t*, int32_t*);
 #define ORX_I_ENV(N, G, X)                                                                      \
   ORX_INST template __global__ void env_step_kernel<N, G, X>(                                   \
       orx_cfg_t, orx_state_t, const void*, int32_t, int32_t, int32_t, int8_t*, int32_t*, float*, \
@@ -5581,11 +5458,7 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
   ORX_INST template __global__ void replay_kernel<N, R, E>(orx_cfg_t, orx_state_t,              \
                                                            const int8_t*, int32_t, int32_t*,    \
                                                            uint32_t, Key, uint32_t, uint32_t);
-#define ORX_I_MOV_STEP(N, E, G)                                                                 \
-  ORX_INST template __global__ void step_kernel<N, E, G, true, true>(                           \
-      orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*);      \
-  ORX_INST template __global__ void mt_step_kernel<N, E, G, true>(                              \
-      orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*);
+#define ORX_I_MOV_STEP(N, E, G) ORX_I_STEP_M(N, E, G, true, false) ORX_I_STEP_M(N, E, G, true, true)
 #define ORX_I_MOV_NG(N, G)                                                                      \
   ORX_INST template __global__ void step_n_kernel<N, G, true>(orx_cfg_t, orx_state_t,           \
                                                               const int8_t*, int32_t, int32_t*, \
@@ -5593,10 +5466,12 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
   ORX_INST template __global__ void env_step_kernel<N, G, true, true>(                          \
       orx_cfg_t, orx_state_t, const void*, int32_t, int32_t, int32_t, int8_t*, int32_t*, float*, \
       uint8_t*, int32_t*, uint32_t*, uint32_t, Key, uint32_t, int32_t, uint32_t);
-#define ORX_I_MOV_ROLLOUT(N, G, M)                                                              \
-  ORX_INST template __global__ void mov_rollout_kernel<N, G, M>(                                \
+#define ORX_I_LANE_ROLLOUT(N, G, MT, MOV)                                                       \
+  ORX_INST template __global__ void lane_rollout_kernel<N, G, MT, MOV>(                         \
       orx_cfg_t, orx_state_t, int32_t, int32_t, int32_t, int32_t*, int8_t*, uint32_t, Key,      \
       uint32_t, int32_t, uint32_t);
+#define ORX_I_MT_ROLLOUT(N, G) ORX_I_LANE_ROLLOUT(N, G, true, false)
+#define ORX_I_MOV_ROLLOUT(N, G, M) ORX_I_LANE_ROLLOUT(N, G, M, true)
 #define ORX_I_STAIRS(G)                                                                         \
   ORX_INST template __global__ void stairs_kernel<G>(orx_cfg_t, orx_state_t, const uint32_t*,    \
                                                      const int32_t*, const int32_t*,            \
@@ -5642,7 +5517,6 @@ ORX_ENV_LIST(ORX_I_ENV)
 #if ORX_OWNS(11)
 ORX_STEP_LIST(ORX_I_STEP)
 ORX_STEP_REF_LIST(ORX_I_STEP_REF)
-ORX_STEP_LIST(ORX_I_MT_STEP)
 #endif
 #if ORX_OWNS(13)
 ORX_PAIR_LIST_M(ORX_I_PAIR, 0)
@@ -5989,8 +5863,8 @@ static int launch_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t
 #define ORX_STEP_ARGS B, s, *cfg, *st, actions, B, k, off, events, n_events
 #define ORX_STEP(NC, E, G, MOV)                                                                 \
   if (nc == NC && ev == E && grid == G)                                                         \
-    return mt ? launch(name, mt_step_kernel<NC, E, G, MOV>, ORX_STEP_ARGS)                      \
-              : launch(name, step_kernel<NC, E, G, true, MOV>, ORX_STEP_ARGS);
+    return launch(name, mt ? step_kernel<NC, E, G, true, MOV, true>                             \
+                           : step_kernel<NC, E, G, true, MOV, false>, ORX_STEP_ARGS);
 #define ORX_STEP_MOV(NC, E, G) ORX_STEP(NC, E, G, true)
 #define ORX_STEP_STAY(NC, E, G) ORX_STEP(NC, E, G, false)
 #define ORX_STEP_REF(NC)                                                                        \
@@ -6212,14 +6086,12 @@ int orx_rollout_ex(const orx_cfg_t* cfg, const orx_state_t* st, int32_t policy_p
   const bool mt = cfg->rng == ORX_RNG_MT19937;
   const bool sep = (cfg->flags & ORX_EXT_SEPARATION_DAMAGE) != 0;
   constexpr int kRefused = 1;  // (no ORX_* code: the runtime refused the plan's LDS limit raise)
-#define ORX_MOV_ROLLOUT(N, G, M)                                                                \
-  if (nc == N && grid == G && mt == M)                                                          \
-    return launch("orx_rollout", mov_rollout_kernel<N, G, M>, p, s, *cfg, *st, policy_p1,       \
-                  policy_p2, n_ticks, obs, act, B, k, off, obs_format, p.lanes);
-#define ORX_MT_ROLLOUT(N, G)                                                                    \
-  if (nc == N && grid == G)                                                                     \
-    return launch("orx_rollout", mt_rollout_kernel<N, G>, p, s, *cfg, *st, policy_p1,           \
-                  policy_p2, n_ticks, obs, act, B, k, off, obs_format);
+#define ORX_LANE_ROLLOUT(N, G, MT, MOV)                                                         \
+  if (nc == N && grid == G && mt == MT)                                                         \
+    return launch("orx_rollout", lane_rollout_kernel<N, G, MT, MOV>, p, s, *cfg, *st,           \
+                  policy_p1, policy_p2, n_ticks, obs, act, B, k, off, obs_format, p.lanes);
+#define ORX_MOV_ROLLOUT(N, G, M) ORX_LANE_ROLLOUT(N, G, M, true)
+#define ORX_MT_ROLLOUT(N, G) ORX_LANE_ROLLOUT(N, G, true, false)
 #define ORX_PAIR(N, P, A, S, C, G)                                                              \
   if (nc == N && p.pm == P && (A == kStreamAux) == p.nt && S == (P == 2 && sep) && C == cf &&   \
       G == grid)                                                                                \
@@ -6255,6 +6127,7 @@ int orx_rollout_ex(const orx_cfg_t* cfg, const orx_state_t* st, int32_t policy_p
 #undef ORX_PAIR
 #undef ORX_MT_ROLLOUT
 #undef ORX_MOV_ROLLOUT
+#undef ORX_LANE_ROLLOUT
   const RolloutRequest q{cfg, policy_p1, policy_p2, B, obs && act, cf, (uint32_t)concurrency};
   const Env env = read_env();
   const Device dev = device();

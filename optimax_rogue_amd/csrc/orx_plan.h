@@ -102,8 +102,8 @@ inline Env read_env() {
 }
 
 enum class Form {
-  kMoving,   // the moving-NPC kernels (mov_rollout_kernel, step_n_kernel / env_step_kernel MOV)
-  kMt,       // stock-seed mode (mt_rollout_kernel)
+  kMoving,   // the moving-NPC kernels (lane_rollout_kernel / step_n_kernel / env_step_kernel MOV)
+  kMt,       // stock-seed mode (lane_rollout_kernel<N, G, true, false>)
   kPaired,   // pair_rollout_kernel: two lanes per game
   kOneLane,  // rollout_kernel: one lane per game
   kReplay,   // replay_kernel: orx_step_n's one-lane replay under the rollout's tick

@@ -435,7 +435,7 @@ def test_env_step_games_per_wave_invariance(cfgname, B, monkeypatch):
 @pytest.mark.parametrize("cfgname,B", [("random16", 1537), ("chase8", 999), ("dense", 333),
                                        ("stock", 257)])
 def test_moving_rollout_games_per_wave_invariance(cfgname, B, monkeypatch):
-    """mov_rollout_kernel at 64, 16 and 1 games per wave (ORX_MOV_LANES)
+    """lane_rollout_kernel at 64, 16 and 1 games per wave (ORX_MOV_LANES)
     writes identical rows and actions and leaves identical state, with
     partial waves and workgroups, autoresets inside the launch, dense NPCs
     and stock-seed mode."""

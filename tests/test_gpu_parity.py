@@ -193,13 +193,47 @@ ORACLE_CASES = {
     "mnpc_ext": (dict(width=8, height=8, start_mode=2, p1_depth=0, p2_depth=1, n_npcs=9,
                       npc_damage=2, max_ticks=0, flags=3, sep_period=3, npc_policy=2), (2, 1),
                  2048, 300, 67),
+    # one case per instance family of the one-lane step and rollout kernels
+    # that no case above reaches: stock-seed mode with 9..16 NPCs, with a
+    # bank without NPCs and with a bank under dense NPCs; moving NPCs in
+    # stock-seed mode beyond 8 NPCs and on a bank; keyed moving NPCs on a bank
+    # with up to 8 and with dense NPCs
+    "stock_npc16": (dict(width=12, height=12, n_npcs=12, max_ticks=150, rng=1), (1, 2), 1024, 200,
+                    70),
+    "stock_bank_npc16": (dict(width=12, height=10, n_npcs=11, despawn=2, max_ticks=150, rng=1),
+                         (2, 1), 1024, 200, 71),
+    "stock_bank_empty": (dict(width=12, height=10, max_ticks=150, rng=1), (2, 1), 1024, 200, 72),
+    "stock_bank_dense": (dict(width=12, height=10, n_npcs=24, max_ticks=150, start_mode=2,
+                              p1_depth=1, p2_depth=0, rng=1), (2, 1), 1024, 200, 73),
+    "mnpc_stock_16": (dict(width=12, height=12, n_npcs=12, max_ticks=100, rng=1, npc_policy=1),
+                      (1, 2), 1024, 200, 74),
+    "mnpc_stock_dense": (dict(width=12, height=12, n_npcs=30, npc_health=2, max_ticks=100, rng=1,
+                              npc_policy=2), (2, 1), 1024, 200, 75),
+    "mnpc_stock_bank": (dict(width=12, height=10, n_npcs=6, max_ticks=100, rng=1, npc_policy=1),
+                        (1, 2), 1024, 200, 76),
+    "mnpc_stock_bank_16": (dict(width=12, height=10, n_npcs=10, max_ticks=100, rng=1,
+                                npc_policy=2), (2, 1), 1024, 200, 77),
+    "mnpc_stock_bank_dense": (dict(width=12, height=10, n_npcs=24, max_ticks=100, rng=1,
+                                   npc_policy=1), (2, 2), 1024, 200, 78),
+    "mnpc_bank_8": (dict(width=12, height=10, n_npcs=6, max_ticks=100, npc_policy=1), (1, 2),
+                    1024, 200, 79),
+    "mnpc_bank_dense": (dict(width=12, height=10, n_npcs=24, max_ticks=100, npc_policy=2), (2, 1),
+                        1024, 200, 80),
 }
 ORACLE_BANKS = {"bank_64_npc": (64, 64, 16, 21, (1,)), "bank_stairs_unused": (12, 10, 5, 22, (1, 3)),
                 "npc_dense_bank": (12, 10, 6, 46, (1, 2)),
                 "bank_big_global": (36, 36, 64, 27, (1, 2)),
                 "stock_bank_separated": (12, 10, 7, 24, (1, 2)),
                 "npc_stair_unused_bank": (8, 7, 6, 50, (1, 2)),
-                "mnpc_chase_bank": (12, 10, 5, 51, (1, 2))}
+                "mnpc_chase_bank": (12, 10, 5, 51, (1, 2)),
+                "stock_bank_npc16": (12, 10, 5, 52, (1, 2)),
+                "stock_bank_empty": (12, 10, 5, 53, (1, 2)),
+                "stock_bank_dense": (12, 10, 5, 54, (1, 2)),
+                "mnpc_stock_bank": (12, 10, 5, 55, (1, 2)),
+                "mnpc_stock_bank_16": (12, 10, 5, 56, (1, 2)),
+                "mnpc_stock_bank_dense": (12, 10, 5, 57, (1, 2)),
+                "mnpc_bank_8": (12, 10, 5, 58, (1, 2)),
+                "mnpc_bank_dense": (12, 10, 5, 59, (1, 2))}
 
 
 @pytest.mark.parametrize("name", sorted(ORACLE_CASES))
@@ -721,7 +755,7 @@ def test_bench_sharded_extras_vs_oracle(name, oracle_lib):
 def test_bench_moving_extras_vs_oracle(npc_policy, oracle_lib):
     """bench.py's c3_moving_npcs / c3_chasing_npcs extras as they are timed
     (rollout_rate: C3 with npc_policy RANDOM / CHASE, 65,536 games, seed 5,
-    2x RandomBot, one stream, int32 rows + actions; mov_rollout_kernel), for
+    2x RandomBot, one stream, int32 rows + actions; lane_rollout_kernel), for
     3 back-to-back 128-tick launches: every game's state after each launch
     against a threaded oracle over the batch, and 8-game windows replayed
     tick by tick (every observation row and action pair) -- the reference's

@@ -1,11 +1,12 @@
-"""A/B of the moving-NPC rollout (mov_rollout_kernel) over games per wave
+"""A/B of the moving-NPC rollout (lane_rollout_kernel<N, G, MT, true>) over games per wave
 (env ORX_MOV_LANES, read per launch): bench.py's c3_moving_npcs /
 c3_chasing_npcs shape (C3 with npc_policy RANDOM / CHASE, 65,536 games,
 2x RandomBot, 128 ticks, int32 rows + actions), median of 10 launches between
 HIP events per form; every form's rows and final state are checked equal to
-the first form's.  Prints one JSON line per policy and round.
+the first form's.  Prints one JSON line per policy and round.  --lib loads
+another build of the library (an A/B against a parent's liborx.so).
 
-    python tools/ab_mov.py [rounds] [lanes,...]
+    python tools/ab_mov.py [rounds] [lanes,...] [--lib=PATH]
 """
 import json
 import os
@@ -16,8 +17,13 @@ sys.path.insert(0, ROOT)
 
 
 def main():
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    forms = sys.argv[2].split(",") if len(sys.argv) > 2 else ["64", "32", "16"]
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    opts = dict(a[2:].split("=", 1) for a in sys.argv[1:] if a.startswith("--") and "=" in a)
+    rounds = int(args[0]) if args else 2
+    forms = args[1].split(",") if len(args) > 1 else ["64", "32", "16"]
+    if "lib" in opts:
+        from optimax_rogue_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(opts["lib"])
     import torch
     from optimax_rogue_amd import EnvConfig, NpcPolicy, OBS_FIELDS, Policy
     from optimax_rogue_amd.engine import BatchedEngine

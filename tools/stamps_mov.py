@@ -1,6 +1,6 @@
 """Where the moving-NPC rollout's cycles go (diagnostics; needs a build with
 -DORX_STAMPS, `python -m optimax_rogue_amd.build --variant stamps`): one
-mov_rollout_kernel launch at bench.py's c3_moving_npcs / c3_chasing_npcs
+lane_rollout_kernel launch at bench.py's c3_moving_npcs / c3_chasing_npcs
 shape (C3 with npc_policy RANDOM / CHASE, 65,536 games, 2x RandomBot, 128
 ticks, int32 rows + actions); per wave, the shader-clock cycles of each
 section summed over the launch by the wave's first active lane (slots of
