@@ -51,15 +51,10 @@ VARIANTS = {
     "stamps": ("ORX_STAMPS",),    # per-wave s_memtime stamps + rare-block counts
     "diag64": ("ORX_DIAG=64",),   # the paired RandomBot tick block without Philox
     "noremap": ("ORX_XCD_REMAP=0",),  # workgroups in dispatch order (no XCD-aware remap)
-    "lean": ("ORX_LEAN=1",),      # the paired StaircaseBot form with its lean spans (rejected)
-    "split1": ("ORX_SPLIT_TICK=1",),  # split tick blocks in the compact form (rejected)
-    "split2": ("ORX_SPLIT_TICK=2",),  # split tick blocks in every paired RandomBot form (rejected)
-    "sepw0": ("ORX_SEP_WAVES=0",),    # the separation-damage StaircaseBot form uncapped (131 VGPRs)
     "envw5": ("ORX_ENV_WAVES=5",),    # orx_env_step_ex held to 5 waves per SIMD
     "envw6": ("ORX_ENV_WAVES=6",),    # ... to 6
     "envd1": ("ORX_ENV_DIAG=1",),     # orx_env_step without its tick (outputs of the loaded state)
     "envd2": ("ORX_ENV_DIAG=2",),     # orx_env_step without its observation rows
-    "routl": ("ORX_RARE_OUTLINE=1",),  # the paired fallback rare tick out of line (rejected)
 }
 
 

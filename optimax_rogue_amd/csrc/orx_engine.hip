@@ -31,11 +31,15 @@
 //   * World.dungeons membership is derived from the players' start and
 //     current depths (DESIGN.md "Dungeon presence").
 //
-// Performance structure (gfx950, one wave per SIMD at the 65,536-game config):
-//   * the common tick is straight-line: the per-tick random words (policy and
-//     initiative streams, two Philox blocks each) are generated unconditionally
-//     and interleaved, accepted words are picked with selects; only lanes that
-//     exhaust 8 words take the generic stream loop (rare);
+// Performance structure (gfx950; DESIGN.md s4 "The tick block", s7):
+//   * the common tick is straight-line: one Philox block per game-tick is the
+//     tick's bit reservoir -- word 0 the initiative shuffle's 2-bit fields,
+//     words 1 and 2 the bots' 3-bit fields -- and the first accepted fields
+//     are picked bit-parallel (a mask and a count-trailing-zeros); only a
+//     game whose segment holds too few takes the next word, then its
+//     purpose's own stream (rare, capped at kWordCap words);
+//   * at the 65,536-game config the paired rollout runs a game on two lanes,
+//     so two 32-game waves share a SIMD (s7.1);
 //   * Philox rounds use v_mad_u64_u32 (64-bit product) and SGPR key schedule;
 //   * NPC occupancy is a packed 16-bit compare against registers (NCAP slots,
 //     a template parameter: 0, 8 or 16), dead slots hold 0xFFFF (no target);
@@ -99,6 +103,12 @@ __device__ uint64_t g_stamps[65536 * 16];
   if ((threadIdx.x & 63) == 0)                                                     \
     g_stamps[(size_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 16 + (j)] =   \
         __builtin_amdgcn_s_memtime()
+// a stamp taken once the wave's loads and stores have landed
+#define ORX_STAMP_SYNC(j)                                \
+  do {                                                   \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     \
+    ORX_STAMP(j);                                        \
+  } while (0)
 // per-wave counts of rare-block entries (stamp slots 5..7): the block's first
 // active lane counts the entry; the lanes' counts are summed at the end
 #define ORX_COUNT(var)                                                                   \
@@ -118,18 +128,33 @@ __device__ uint64_t g_stamps[65536 * 16];
   atomicAdd((unsigned long long*)&g_stamps[(size_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * \
                                                16 + (j)],                                  \
             (unsigned long long)(__builtin_amdgcn_s_memtime() - (v)))
+// the rollout kernels' epilogue: a launch's counts and cycles (a Deltas'
+// stamps members), summed over the wave, into its stamp slots 5..14
+template <class D>
+__device__ __forceinline__ void stamp_counts(const D& dl) {
+  uint32_t r[10] = {dl.n_rare, dl.n_ordered, dl.n_hits, dl.n_desc, dl.n_meet, dl.n_reset,
+                    dl.cy_rare, dl.cy_reset, dl.cy_ordered, dl.cy_desc};
+#pragma unroll
+  for (int j = 0; j < 10; ++j)
+    for (int o = 32; o > 0; o >>= 1) r[j] += __shfl_xor(r[j], o);
+  if ((threadIdx.x & 63) == 0) {
+    const size_t w = (size_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 16;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) g_stamps[w + 5 + j] = r[j];
+  }
+}
+#define ORX_STAMP_COUNTS(dl) stamp_counts(dl)
 #else
 #define ORX_STAMP(j) ((void)0)
+#define ORX_STAMP_SYNC(j) ((void)0)
+#define ORX_STAMP_COUNTS(dl) ((void)0)
 #define ORX_COUNT(var) ((void)0)
 #define ORX_CYC_BEGIN(v) ((void)0)
 #define ORX_CYC_END(var, v) ((void)0)
 #define ORX_MCYC_BEGIN(v) ((void)0)
 #define ORX_MCYC_END(j, v) ((void)0)
 #endif
-#ifndef ORX_ROLLOUT_BLOCK
-#define ORX_ROLLOUT_BLOCK 256
-#endif
-constexpr int kRolloutBlock = ORX_ROLLOUT_BLOCK;  // rollout_kernel workgroup size
+constexpr int kRolloutBlock = ORX_ROLLOUT_BLOCK;  // rollout_kernel workgroup size (orx_plan.h)
 // Games per rollout wave ("lanes", a power of two 1..64) is a launch
 // argument: below 64 the wave's upper lanes idle so that a small batch still
 // puts a wave on every SIMD (orx_rollout picks it from the batch and the CU
@@ -137,23 +162,6 @@ constexpr int kRolloutBlock = ORX_ROLLOUT_BLOCK;  // rollout_kernel workgroup si
 
 #ifndef ORX_XCD_REMAP
 #define ORX_XCD_REMAP 1
-#endif
-#ifndef ORX_SPLIT_TICK
-// pair_rollout_kernel's RandomBot tick blocks (PM 1), one Philox pass per two
-// ticks: lane 2j draws tick t's block and lane 2j+1 tick t+1's, the pair
-// swaps them, and the next trip uses the held block (a reset redraws).  1:
-// the compact-row form only; 2: every PM 1 form; 0 (the product): none --
-// measured in round 5 (profiles/r05_v5/ab_forms.jsonl, three rounds on one
-// box): compact rows 73.2-74.3 us with it against 73.1-75.1 without, the
-// int32 headline step 88.1-89.1 against 85.0-86.5 and C2 49.7-50.0 against
-// 47.9-48.5 (as in round 3, profiles/r03_v11).
-#define ORX_SPLIT_TICK 0
-#endif
-#ifndef ORX_LEAN
-// pair_rollout_kernel's lean StaircaseBot spans: off (measured slower, DESIGN
-// s7.2: the launch is set by its slowest waves, which run few lean ticks and
-// pay the span computation on every general tick); -DORX_LEAN=1 builds them
-#define ORX_LEAN 0
 #endif
 // The rollout kernels' workgroup order, XCD-aware: the dispatcher deals
 // workgroups round-robin over the chip's 8 XCDs (workgroup b to XCD b % 8),
@@ -353,7 +361,6 @@ struct Deltas {  // counter / return increments, flushed once per launch
 #ifdef ORX_STAMPS
   uint32_t n_rare = 0, n_ordered = 0, n_hits = 0, n_desc = 0, n_meet = 0,  // rare-block entries
            n_reset = 0;
-  uint32_t n_lean = 0;  // lean ticks (pair_rollout_kernel's StaircaseBot spans)
   uint32_t cy_rare = 0, cy_reset = 0, cy_ordered = 0, cy_desc = 0;  // cycles in them
 #endif
 };
@@ -2923,18 +2930,15 @@ __global__ void __launch_bounds__(256) reset_kernel(orx_cfg_t hc, orx_state_t st
 // code compiled out -- fewer registers, so more waves per SIMD hide the
 // state loads (the per-tick drop-in's common case)
 // One game's Updater.update (or its autoreset): the per-tick step kernels'
-// body.  get_action(p1, p2, tick, ep, tb) yields the game's packed action pair
-// (player 1 in the low byte).  Without an output callback (NoOut: the step
-// kernels) it is called only for a game in progress, with p1 / p2 / tick /
-// ep / tb not loaded.  With one (env_step_kernel) every state word is loaded
-// up front -- one round trip for the whole launch -- get_action sees the
-// pre-tick players and the tick block for every game (one Philox block serves
-// player 2's RandomBot and the initiative draw), and out(p1, p2, tick,
-// status) receives the post-step state from registers (no re-read of what
-// was just stored).
-#ifndef ORX_STEP_EAGER
-#define ORX_STEP_EAGER 1
-#endif
+// body.  Every state word and the action pair are loaded up front, in one
+// round trip (a finished game discards some; loaded behind the status and
+// action tests, a game in progress waited out three round trips in a row).
+// get_action(p1, p2, tick, ep, tb) yields the game's packed action pair
+// (player 1 in the low byte) from the pre-tick players, for every game.  With
+// an output callback (env_step_kernel; NoOut: the step kernels have none) tb
+// is the tick block -- one Philox block serves player 2's RandomBot and the
+// initiative draw -- and out(p1, p2, tick, status) receives the post-step
+// state from registers (no re-read of what was just stored).
 struct NoOut {
   __device__ __forceinline__ void operator()(const Player&, const Player&, int32_t, int32_t) {}
 };
@@ -2945,10 +2949,6 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
                                           int32_t* __restrict__ events,
                                           int32_t* __restrict__ n_events, O out = O{}) {
   constexpr bool kOut = !std::is_same<O, NoOut>::value;
-  // every state word and the action pair in one round trip (a finished game
-  // discards some) -- the step kernels too: loaded behind the status and
-  // action tests, a game in progress waited out three round trips in a row
-  constexpr bool kEager = kOut || ORX_STEP_EAGER;
   Cfg c = make_cfg(hc, st);
   if constexpr (!EXT) c.ext = 0;
   const uint32_t game = off + i;
@@ -2956,32 +2956,26 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
   Npcs<NCAP> npc;
   npc.bind(st, c, B, i);
   Player p1, p2;
-  int32_t tick = 0;
-  uint32_t ep = 0;
-  uint16_t a = 0;
   Items<NCAP> items;
   int32_t sep = -1;
   W4 tb0{0, 0, 0, 0};  // (kOut) the tick block: player 2's policy and the initiative draw
   Src src = Src::make(key, game, 0u);
-  if constexpr (kEager) {
-    load_players<GRID>(st, B, i, p1, p2);
-    tick = st.tick[i];
-    ep = (uint32_t)st.episode[i];
-    src.open(st, c, B, i);  // (stock-seed mode: the streams' indices with the state words)
-    load_npcs(st, c, B, i, npc);
-    load_rpg(st, c, B, i, p1, p2, npc, items);
-    if (c.ext & ORX_EXT_SEPARATION_DAMAGE) sep = st.sep_start[i];
-    if constexpr (kOut) tb0 = tick_block(key, game, ep, tick);
-    a = get_action(p1, p2, tick, ep, tb0);
-  }
+  load_players<GRID>(st, B, i, p1, p2);
+  int32_t tick = st.tick[i];
+  const uint32_t ep = (uint32_t)st.episode[i];
+  src.open(st, c, B, i);  // (stock-seed mode: the streams' indices with the state words)
+  load_npcs(st, c, B, i, npc);
+  load_rpg(st, c, B, i, p1, p2, npc, items);
+  if (c.ext & ORX_EXT_SEPARATION_DAMAGE) sep = st.sep_start[i];
+  if constexpr (kOut) tb0 = tick_block(key, game, ep, tick);
+  const uint16_t a = get_action(p1, p2, tick, ep, tb0);
   if (status != ORX_IN_PROGRESS) {
     if (EV) n_events[i] = 0;
     if (!c.autoreset) {
       out(p1, p2, tick, status);
       return;
     }
-    const uint32_t ep1 = (kEager ? ep : (uint32_t)st.episode[i]) + 1u;
-    if constexpr (!kEager) src.open(st, c, B, i);
+    const uint32_t ep1 = ep + 1u;
     src.episode(ep1);
     setup_game<NCAP, GRID>(c, key, src, p1, p2, npc, tick, status);
     src.close();  // (stock-seed mode: the streams' indices, before the state)
@@ -2999,7 +2993,6 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
     out(p1, p2, tick, status);
     return;
   }
-  if constexpr (!kEager) a = get_action(p1, p2, tick, ep, tb0);
   p1.move = (int8_t)(a & 0xFF);
   p2.move = (int8_t)(a >> 8);
   if (!valid_move(c, p1.move) || !valid_move(c, p2.move)) {
@@ -3007,15 +3000,6 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
     if (EV) n_events[i] = 0;
     out(p1, p2, tick, (int32_t)ORX_STATUS_BAD_ACTION);
     return;
-  }
-  if constexpr (!kEager) {
-    ep = (uint32_t)st.episode[i];
-    tick = st.tick[i];
-    load_players<GRID>(st, B, i, p1, p2);
-    load_npcs(st, c, B, i, npc);
-    load_rpg(st, c, B, i, p1, p2, npc, items);
-    if (c.ext & ORX_EXT_SEPARATION_DAMAGE) sep = st.sep_start[i];
-    src.open(st, c, B, i);
   }
   src.episode(ep);
   NpcMem m{st.npc_pos, st.npc_health, B, i};
@@ -3367,10 +3351,8 @@ __device__ __forceinline__ bool rare_tick(const Cfg& c, const orx_state_t& st, u
   const bool end = c.max_ticks && ft >= c.max_ticks;
   if (!in_progress) {
     if (c.autoreset) {  // the next episode (worldgen.py:77-87, 124-135)
-#ifdef ORX_STAMPS
       ORX_COUNT(dl.n_reset);
       ORX_CYC_BEGIN(cy1);
-#endif
       ep += 1;
       setup_game<NCAP, GRID>(c, key, game, ep, p1, p2, npc, tick, status);
       items.clear();
@@ -3384,23 +3366,17 @@ __device__ __forceinline__ bool rare_tick(const Cfg& c, const orx_state_t& st, u
       }
       restarted = true;
       sep = -1;
-#ifdef ORX_STAMPS
       ORX_CYC_END(dl.cy_reset, cy1);
-#endif
     }
   } else if (full) {  // the ordered tick
-#ifdef ORX_STAMPS
     ORX_COUNT(dl.n_ordered);
     ORX_CYC_BEGIN(cy1);
-#endif
     bool err = false;
     const bool p1_first = first_from_packed(pk_shf, key, game, ep, t0, err);
     Events<false> ev{nullptr, 0};
     tick_game<NCAP, false, GRID>(c, key, game, ep, p1_first, p1, p2, npc, items, hp, tick,
                                  status, err, dl, ev, sep);
-#ifdef ORX_STAMPS
     ORX_CYC_END(dl.cy_ordered, cy1);
-#endif
   } else {
     // the common path's rules, then the one-sided events: a player that
     // hits an NPC, descends or meets the other does not move freely
@@ -3417,24 +3393,18 @@ __device__ __forceinline__ bool rare_tick(const Cfg& c, const orx_state_t& st, u
     bool desc_done = false;  // fast_descend finished it
     if constexpr (!GRID) {
       if (!lean & (st1 | st2)) {
-#ifdef ORX_STAMPS
         ORX_CYC_BEGIN(cyf);
-#endif
         // the other player has made its move above
         desc_done = fast_descend<NCAP>(c, key, game, ep, t0, st1, p1, p2,
                                        st1 ? x2o : x1o, st1 ? y2o : y1o,
                                        st1 ? p2.x : p1.x, st1 ? p2.y : p1.y, npc, dl);
-#ifdef ORX_STAMPS
         if (desc_done) ORX_COUNT(dl.n_desc);
         ORX_CYC_END(dl.cy_desc, cyf);
-#endif
       }
     }
     if (!lean & (st1 | st2) & !desc_done) {  // one player descends: the general form
-#ifdef ORX_STAMPS
       ORX_COUNT(dl.n_desc);
       ORX_CYC_BEGIN(cy1);
-#endif
       PhiloxSrc src{key, game, ep};
       auto spawn = src.spawn(t0);
       Events<false> ev{nullptr, 0};
@@ -3467,15 +3437,11 @@ __device__ __forceinline__ bool rare_tick(const Cfg& c, const orx_state_t& st, u
         status = ORX_STATUS_RNG_EXHAUSTED;
       }
       if (clash) deaths_over(p1, p2, end, status, dl);
-#ifdef ORX_STAMPS
       ORX_CYC_END(dl.cy_desc, cy1);
-#endif
     }
     bool kc1 = false, kc2 = false;  // ORX_EXT_LEVELING: each player's kill this tick
     if (NCAP > 0 && (hit1 | hit2)) {  // NPCs are swept after both moves
-#ifdef ORX_STAMPS
       ORX_COUNT(dl.n_hits);
-#endif
       Events<false> ev{nullptr, 0};
       dl.combat += (hit1 ? 1 : 0) + (hit2 ? 1 : 0);
       int32_t d1 = c.player_dmg_net > 0 ? c.player_dmg_net : 0, d2 = d1;
@@ -3505,9 +3471,7 @@ __device__ __forceinline__ bool rare_tick(const Cfg& c, const orx_state_t& st, u
       }
     }
     if (lean) {  // a meet: the two moves in the drawn order
-#ifdef ORX_STAMPS
       ORX_COUNT(dl.n_meet);
-#endif
       const uint32_t sa = ~(pk_shf >> 1) & 0x55555555u;  // nonzero: all-reject is ordered
       const bool p1_first = ((pk_shf >> __builtin_ctz(sa)) & 1u) != 0;
       const int32_t ax = p1_first ? t1x : t2x, ay = p1_first ? t1y : t2y;
@@ -3694,16 +3658,12 @@ __device__ __forceinline__ void rollout_tick(const Cfg& c, const orx_state_t& st
   // are never live together, so the loop carries no register copies).
   bool took_ordered = false;  // the ordered tick ran (it applies its own extensions)
   if (ORX_UNLIKELY(rare)) {
-#ifdef ORX_STAMPS
     ORX_COUNT(dl.n_rare);
     ORX_CYC_BEGIN(cy0);
-#endif
     took_ordered = rare_tick<NCAP, GRID>(c, st, B, i, key, game, ep, p1, p2, npc, items, hp,
                                          tick, status, dl, sep, restarted, tb, need, t1x,
                                          t1y, t2x, t2y, ext_ordered | heal, bad);
-#ifdef ORX_STAMPS
     ORX_CYC_END(dl.cy_rare, cy0);
-#endif
   }
   // the common tick: both players move to their effective targets
   p1.x = rare ? p1.x : t1x;
@@ -3805,11 +3765,7 @@ struct TrajWriter {
     if constexpr (FAST) {
 #pragma unroll
       for (int f = 0; f < kRows; ++f) {
-#ifdef ORX_OBS_TILED  // diagnostic: [T][B/64][14][64] tiles (B a multiple of 64)
-        vo[f] = ((i >> 6) * (uint32_t)kRows * 64u + (uint32_t)f * 64u + (i & 63u)) * 4u;
-#else
         vo[f] = i * 4u + (uint32_t)f * B * 4u;
-#endif
         asm volatile("" : "+v"(vo[f]));
       }
       va = i * 2u;
@@ -3970,19 +3926,14 @@ __global__ void __launch_bounds__(kRolloutBlock) rollout_kernel(orx_cfg_t hc, or
     launder(p1.lay, p2.lay, tick, status);
     asm volatile("" : "+v"(sep), "+v"(ep));
   }
-#ifdef ORX_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  ORX_STAMP(1);
+  ORX_STAMP_SYNC(1);
   int32_t t = 0;
   // the FAST writers' exit test on the row pointer (a scalar register; a test
   // on t gets t a VGPR: 2 VALU a tick, as in pair_rollout_kernel)
   const int32_t* const obs_end =
       kTraj ? obs + (size_t)n_ticks * TrajWriter<kTraj, AUX, CF>::kRows * B : nullptr;
   do {  // n_ticks >= 1: orx_rollout returns before launching 0 ticks
-#ifdef ORX_STAMPS
     if (t == 64) { ORX_STAMP(2); }
-#endif
     int32_t a1 = ORX_MOVE_STAY, a2 = ORX_MOVE_STAY;
     if (!(ORX_DIAG & 32))
       rollout_tick<NCAP, GRID>(c, st, B, i, key, game, ep, pol1, pol2, p1, p2, npc, items, hp,
@@ -4004,22 +3955,8 @@ __global__ void __launch_bounds__(kRolloutBlock) rollout_kernel(orx_cfg_t hc, or
       if (restarted || dl.combat) hp.store(st.npc_health, c.K, B, i);
   }
   flush_deltas(st, B, i, dl);
-#ifdef ORX_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  ORX_STAMP(4);
-#ifdef ORX_STAMPS
-  uint32_t r[11] = {dl.n_rare, dl.n_ordered, dl.n_hits, dl.n_desc, dl.n_meet, dl.n_reset,
-                    dl.cy_rare, dl.cy_reset, dl.cy_ordered, dl.cy_desc, dl.n_lean};
-#pragma unroll
-  for (int j = 0; j < 11; ++j)
-    for (int o = 32; o > 0; o >>= 1) r[j] += __shfl_xor(r[j], o);
-  if ((threadIdx.x & 63) == 0) {
-    const size_t w = (size_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 16;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) g_stamps[w + 5 + j] = r[j];
-  }
-#endif
+  ORX_STAMP_SYNC(4);
+  ORX_STAMP_COUNTS(dl);
 }
 
 // ---------------------------------------------------------------------------
@@ -4162,54 +4099,20 @@ struct PairWriter {
 // action rows are stored: the log is the actions); a pair outside the Move
 // codes stops the game in the rare block (orx_step's rule), and the
 // initiative block is drawn only by a rare tick that needs the order.
-// (diagnostic builds may add attributes, e.g. an occupancy target)
-#ifndef ORX_PAIR_ATTR
-#define ORX_PAIR_ATTR
-#endif
-// the StaircaseBot form with separation damage held to four waves per SIMD
+// The StaircaseBot form with separation damage is held to four waves per SIMD
 // (128 VGPRs; 131 otherwise, three waves): C5's 131,072 games as two paired
-// shards are four 32-game waves per SIMD
-#ifndef ORX_SEP_WAVES
-#define ORX_SEP_WAVES 1
-#endif
+// shards are four 32-game waves per SIMD.
 // GRID (round 4): a dungeon bank -- each lane reads its target's tile (its
 // player's layout; LDS-staged when the bank fits, lds_n bytes), a Wall or the
 // grid's edge blocks, ANY staircase tile makes the tick rare; descends and
 // resets take rare_tick's bank forms (the closed-form fast paths are for
 // empty dungeons).
-// The paired rollout's fallback rare tick, out of line (-DORX_RARE_OUTLINE=1,
-// build variant `routl`; measured and rejected): its state goes through a
-// stack frame on the (rare) call, so the common tick and the lean rare
-// branches would not carry the merges of an inlined rare_tick's values.  The
-// call makes the kernel take the callee's registers (196-248 VGPRs, two
-// waves per SIMD) and 464-788 B of scratch per lane, and every paired form
-// slows by a third or more (C3 85 -> 110 us, c3_mixed 155 -> 243, C5's share
-// 64 -> 102; profiles/r06_v7/ab_rare_outline_rejected.jsonl).
-#ifndef ORX_RARE_OUTLINE
-#define ORX_RARE_OUTLINE 0
-#endif
-template <int NCAP, bool GRID, class M>
-__device__ __noinline__ bool rare_tick_ool(const Cfg c, const orx_state_t st, uint32_t B,
-                                           uint32_t i, Key key, uint32_t game, uint32_t& ep,
-                                           Player& p1, Player& p2, Npcs<NCAP>& npc,
-                                           Items<NCAP>& items, M& hp, int32_t& tick,
-                                           int32_t& status, Deltas& dl, int32_t& sep,
-                                           bool& restarted, const W4 tb, int need, int32_t t1x,
-                                           int32_t t1y, int32_t t2x, int32_t t2y) {
-  return rare_tick<NCAP, GRID>(c, st, B, i, key, game, ep, p1, p2, npc, items, hp, tick, status,
-                               dl, sep, restarted, tb, need, t1x, t1y, t2x, t2y, false);
-}
-
 template <int NCAP, int PM, int AUX, bool SEP, bool CF = false, bool GRID = false>
-__global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
-    __attribute__((amdgpu_waves_per_eu(ORX_SEP_WAVES && PM == 2 && SEP ? 4 : 1)))
-    pair_rollout_kernel(orx_cfg_t hc, orx_state_t st,
-                                                                     int32_t n_ticks,
-                                                                     int32_t* __restrict__ obs,
-                                                                     int8_t* __restrict__ act,
-                                                                     uint32_t B, Key key,
-                                                                     uint32_t off, uint32_t lanes,
-                                                                     uint32_t lds_n) {
+__global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock)
+    __attribute__((amdgpu_waves_per_eu(PM == 2 && SEP ? 4 : 1)))
+    pair_rollout_kernel(orx_cfg_t hc, orx_state_t st, int32_t n_ticks, int32_t* __restrict__ obs,
+                        int8_t* __restrict__ act, uint32_t B, Key key, uint32_t off,
+                        uint32_t lanes, uint32_t lds_n) {
   const bool lds_tiles = stage_tiles<GRID>(st, lds_n);
   const uint32_t lane = threadIdx.x & 63u;
   if (lane >= 2u * lanes) return;  // uniform per wave
@@ -4293,73 +4196,14 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
   launder(me.sx, me.sy, me.lay, tick);
   launder(status, sep, me.mana, me.xp);
   launder(me.dmg, me.mhp, me.nitems, reinterpret_cast<int32_t&>(ep));
-#ifdef ORX_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  ORX_STAMP(1);
-  // Lean spans (StaircaseBots on an empty dungeon, C5): both bots walk
-  // greedily to their staircases, so a game's next ticks are plain moves until
-  // a player's target is its staircase (its distance to it, less one), the
-  // two could meet (same depth: the distance between them shrinks by at most
-  // 2 a tick, a meet needs at most 2), the episode ends or, with separation
-  // damage across depths, the next tick's damage would kill.  `span` counts
-  // those ticks from the state a general tick leaves; while every game of the
-  // wave has one left, the wave runs lean ticks: the move, the step, the
-  // separation damage (its ceil(k / period) carried as quotient and remainder,
-  // no division) and the row, nothing else.
-  constexpr bool kLean = ORX_LEAN && PM == 2 && NCAP == 0 && !GRID && (ORX_DIAG & (16 | 32 | 64 | 128)) == 0;
-  // split tick blocks (ORX_SPLIT_TICK): the held block of the next tick and
-  // its key (episode, tick); n_tick -1: none held
-  constexpr bool kSplit = PM == 1 && (ORX_DIAG & 64) == 0 &&
-                          (ORX_SPLIT_TICK == 2 || (ORX_SPLIT_TICK == 1 && CF));
-  W4 nb = {0u, 0u, 0u, 0u};
-  uint32_t nh0 = 0u, nh3 = 0u, n_ep = 0u;
-  int32_t n_tick = -1;
-  int32_t span = 0;
-  int32_t l_od = 0, l_q = 0, l_r = 0;  // SEP: the other's depth; the next tick's damage and phase
+  ORX_STAMP_SYNC(1);
   int32_t t = 0;
   do {
-#ifdef ORX_STAMPS
     if (t == 64) { ORX_STAMP(2); }
-#endif
     if constexpr ((ORX_DIAG & 32) != 0) {  // diagnostic: the trajectory stores alone
       tick += 1;
       traj.write(me, kp, ks, isB, tick, status, ORX_MOVE_STAY);
       continue;
-    }
-    if constexpr (kLean) {
-      // the lean ticks as a loop of their own (its values stay in the tick
-      // loop's registers: no copies at a join with the general tick)
-      if (__builtin_amdgcn_ballot_w64(span <= 0) == 0) {  // uniform
-        do {
-          const int32_t dx = me.sx - me.x, dy = me.sy - me.y;
-          const int32_t adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
-          const int32_t mv = adx > ady ? (dx > 0 ? ORX_MOVE_RIGHT : ORX_MOVE_LEFT)
-                                       : (dy > 0 ? ORX_MOVE_DOWN : ORX_MOVE_UP);
-          calc_pos(me.x, me.y, mv, me.x, me.y);
-          span -= 1;
-          if constexpr (SEP) {  // as the common tick's block (readme.md:46-47)
-            if (me.d != l_od) {
-              sep = sep < 0 ? tick : sep;
-              const bool shallow = me.d < l_od;
-              me.hp -= shallow ? l_q : 0;  // ceil(k / period), k = t0 - sep + 1
-              const bool wrap = l_r + 1 == c.sep_period;
-              l_q += wrap ? 1 : 0;
-              l_r = wrap ? 0 : l_r + 1;
-              if (shallow & (me.hp - l_q <= 0)) span = 0;  // the next tick's damage kills
-            } else {
-              sep = -1;
-            }
-          }
-          tick += 1;
-#ifdef ORX_STAMPS
-          ORX_COUNT(dl.n_lean);
-#endif
-          traj.write(me, pack_cell(me.x, me.y), ks, isB, tick, status, mv);
-        } while (++t < n_ticks && __builtin_amdgcn_ballot_w64(span <= 0) == 0);
-        kp = pack_cell(me.x, me.y);
-        if (t >= n_ticks) break;
-      }
     }
     // the bot's move (randombot.py:20-21 / staircasebot.py:9-21)
     W4 tb = {0u, 0u, 0u, 0u};
@@ -4371,28 +4215,6 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
       if constexpr ((ORX_DIAG & 64) != 0) {  // diagnostic: a cheap hash for the tick block
         const uint32_t hsh = (game * 0x9E3779B9u) ^ ((uint32_t)tick * 0x85EBCA6Bu) ^ ep;
         tb = W4{hsh * 0xC2B2AE35u, hsh ^ (hsh >> 15), 0u, 0u};
-      } else if constexpr (kSplit) {
-        const bool have = (ep == n_ep) & (tick == n_tick);
-        if (__builtin_amdgcn_ballot_w64(!have) == 0) {  // uniform: every game holds its block
-          tb = nb;
-          h0 = nh0;
-          h3 = nh3;
-          n_tick = -1;
-        } else {  // one pass for two ticks: lane 2j this tick's block, lane 2j+1 the next's
-          uint32_t m0, m3;
-          const W4 m = philox_ab(game, ep, (uint32_t)(tick + (int32_t)who), tag(PUR_TICK, 0),
-                                 key, m0, m3);
-          const uint32_t oa = (uint32_t)pair_swap((int32_t)m.a), ob = (uint32_t)pair_swap((int32_t)m.b);
-          const uint32_t o0 = (uint32_t)pair_swap((int32_t)m0), o3 = (uint32_t)pair_swap((int32_t)m3);
-          tb = W4{isB ? oa : m.a, isB ? ob : m.b, 0u, 0u};
-          h0 = isB ? o0 : m0;
-          h3 = isB ? o3 : m3;
-          nb = W4{isB ? m.a : oa, isB ? m.b : ob, 0u, 0u};
-          nh0 = isB ? m0 : o0;
-          nh3 = isB ? m3 : o3;
-          n_ep = ep;
-          n_tick = tick + 1;
-        }
       } else {
         tb = philox_ab(game, ep, (uint32_t)tick, tag(PUR_TICK, 0), key, h0, h3);
       }
@@ -4487,10 +4309,8 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
     const bool end = c.max_ticks && ft >= c.max_ticks;
     bool took_ordered = false;
     if (ORX_UNLIKELY(rare)) {
-#ifdef ORX_STAMPS
       ORX_COUNT(dl.n_rare);
       ORX_CYC_BEGIN(cy0);
-#endif
       if constexpr (PM == 1 || PM == 3 || kMixed) {  // the tick block's words c, d (rare_tick's fallbacks)
         asm volatile("" : "+v"(h0), "+v"(h3));
         finish_cd(tb, h0, h3, key);
@@ -4588,9 +4408,7 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
             sep = -1;
             restarted = true;
             fast = true;
-#ifdef ORX_STAMPS
             ORX_COUNT(dl.n_reset);
-#endif
           }
         }
       }
@@ -4617,9 +4435,7 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
           tick = ft;
           status = end ? ORX_TIE : ORX_IN_PROGRESS;
           fast = true;
-#ifdef ORX_STAMPS
           ORX_COUNT(dl.n_hits);
-#endif
         }
       }
       if constexpr (PM == 3 && NCAP > 0) {
@@ -4675,9 +4491,7 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
           tick = ft;
           status = end ? ORX_TIE : ORX_IN_PROGRESS;
           fast = true;
-#ifdef ORX_STAMPS
           ORX_COUNT(dl.n_hits);
-#endif
         }
       }
       if constexpr (PM == 1 || PM == 3 || kMixed || kLog) {
@@ -4720,16 +4534,12 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
             status = sw;
           }
           fast = true;
-#ifdef ORX_STAMPS
           ORX_COUNT(dl.n_meet);
-#endif
         }
       }
       if ((PM == 2 || kMixed || kLog) && !GRID &&
           (in_progress & !meet & (st_me != (st_o != 0)) & !hit_me & (hit_o == 0))) {
-#ifdef ORX_STAMPS
         ORX_CYC_BEGIN(cyf);
-#endif
         const bool dIsB = st_me ? isB : !isB;       // the descender is player 2
         const int32_t sd = st_me ? me.d : od, odep = st_me ? od : me.d;
         const int32_t o_start = dIsB ? c.d1 : c.d2;
@@ -4775,13 +4585,9 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
           tick = ft;
           status = end ? ORX_TIE : ORX_IN_PROGRESS;
           fast = true;
-#ifdef ORX_STAMPS
           ORX_COUNT(dl.n_desc);
-#endif
         }
-#ifdef ORX_STAMPS
         ORX_CYC_END(dl.cy_desc, cyf);
-#endif
       }
       if (!fast) {
         // both lanes rebuild the game's players and run the scalar rare block
@@ -4802,44 +4608,17 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
           o.nitems = pair_swap(me.nitems);
         }
         Player p1 = pick(isB, o, me), p2 = pick(isB, me, o);
-        if constexpr (ORX_RARE_OUTLINE != 0) {
-          // the call's copies: only they live in the frame
-          uint32_t q_ep = ep;
-          Npcs<NCAP> q_npc = npc;
-          Items<NCAP> q_items = items;
-          auto q_hp = hp;
-          int32_t q_tick = tick, q_status = status, q_sep = sep;
-          Deltas q_dl = dl;
-          bool q_restarted = restarted;
-          took_ordered = rare_tick_ool<NCAP, GRID>(c, st, B, i, key, game, q_ep, p1, p2, q_npc,
-                                                   q_items, q_hp, q_tick, q_status, q_dl, q_sep,
-                                                   q_restarted, tb, need, isB ? otx : tx,
-                                                   isB ? oty : ty, isB ? tx : otx,
-                                                   isB ? ty : oty);
-          ep = q_ep;
-          npc = q_npc;
-          items = q_items;
-          hp = q_hp;
-          tick = q_tick;
-          status = q_status;
-          sep = q_sep;
-          dl = q_dl;
-          restarted = q_restarted;
-        } else {
-          took_ordered = rare_tick<NCAP, GRID>(c, st, B, i, key, game, ep, p1, p2, npc, items, hp,
-                                            tick, status, dl, sep, restarted, tb, need,
-                                            isB ? otx : tx, isB ? oty : ty, isB ? tx : otx,
-                                            isB ? ty : oty, false);
-        }
+        took_ordered = rare_tick<NCAP, GRID>(c, st, B, i, key, game, ep, p1, p2, npc, items, hp,
+                                             tick, status, dl, sep, restarted, tb, need,
+                                             isB ? otx : tx, isB ? oty : ty, isB ? tx : otx,
+                                             isB ? ty : oty, false);
         me = pick(isB, p2, p1);
         me.move = move;
       }
       kp = pack_cell(me.x, me.y);
       ks = pack_cell(me.sx, me.sy);
       dk = me.d == c.d1 ? 0u : 0x80008000u;
-#ifdef ORX_STAMPS
       ORX_CYC_END(dl.cy_rare, cy0);
-#endif
     } else {
       kp = kt;
     }
@@ -4876,35 +4655,13 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
         }
       }
     }
-    if constexpr (kLean) {  // the lean ticks from this state on
-      const int32_t ox = pair_swap(me.x), oy = pair_swap(me.y), od = pair_swap(me.d);
-      const int32_t ex = me.sx - me.x, ey = me.sy - me.y;
-      const int32_t dme = (ex < 0 ? -ex : ex) + (ey < 0 ? -ey : ey);  // to my staircase
-      const int32_t dot = pair_swap(dme);
-      const int32_t mx = me.x - ox, my = me.y - oy;
-      const int32_t m = (mx < 0 ? -mx : mx) + (my < 0 ? -my : my);  // between the players
-      int32_t sp = min(dme, dot) - 1;
-      if (me.d == od) sp = min(sp, (m - 1) >> 1);
-      if constexpr (SEP) {
-        l_od = od;
-        if (me.d != od) {  // the next tick's k = t0 - sep + 1 (sep set there if unset)
-          const int32_t P = c.sep_period;
-          const int32_t kn = tick - (sep < 0 ? tick : sep) + 1;
-          l_q = (kn + P - 1) / P;
-          l_r = kn - 1 - (l_q - 1) * P;
-          if ((me.d < od) & (me.hp - l_q <= 0)) sp = 0;
-        }
-      }
-      if (c.max_ticks) sp = min(sp, c.max_ticks - tick - 1);
-      span = status == ORX_IN_PROGRESS ? sp : 0;
-    }
     if (!(ORX_DIAG & 16)) traj.write(me, kp, ks, isB, tick, status, move);
     else traj.skip();
     ++t;
     // the loop's exit test on the row pointer (a scalar register): a test on
     // t alone gets t a VGPR and costs 2 VALU a tick (the compiler takes the
     // counter for divergent in this loop)
-    } while (traj.obs != obs_end);
+  } while (traj.obs != obs_end);
   ORX_STAMP(3);
   st.p_x[who * B + i] = me.x;
   st.p_y[who * B + i] = me.y;
@@ -4944,22 +4701,8 @@ __global__ void __launch_bounds__(GRID ? 512 : kRolloutBlock) ORX_PAIR_ATTR
     }
     flush_deltas(st, B, i, dl);
   }
-#ifdef ORX_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  ORX_STAMP(4);
-#ifdef ORX_STAMPS
-  uint32_t r[11] = {dl.n_rare, dl.n_ordered, dl.n_hits, dl.n_desc, dl.n_meet, dl.n_reset,
-                    dl.cy_rare, dl.cy_reset, dl.cy_ordered, dl.cy_desc, dl.n_lean};
-#pragma unroll
-  for (int j = 0; j < 11; ++j)
-    for (int o = 32; o > 0; o >>= 1) r[j] += __shfl_xor(r[j], o);
-  if ((threadIdx.x & 63) == 0) {
-    const size_t w = (size_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 16;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) g_stamps[w + 5 + j] = r[j];
-  }
-#endif
+  ORX_STAMP_SYNC(4);
+  ORX_STAMP_COUNTS(dl);
 }
 
 // Staircases of arbitrary (game, episode, depth, generation) dungeons, for

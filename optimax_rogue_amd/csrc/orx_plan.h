@@ -16,7 +16,7 @@
 
 extern "C" char** environ;
 
-#ifndef ORX_ROLLOUT_BLOCK  // (orx_engine.hip's compile-time switch and its default)
+#ifndef ORX_ROLLOUT_BLOCK  // (orx_engine.hip's compile-time switch; its one default)
 #define ORX_ROLLOUT_BLOCK 256
 #endif
 

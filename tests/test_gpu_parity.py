@@ -1031,10 +1031,9 @@ PAIRED_CASES.update({
     "bank_rpg": (dict(width=16, height=12, n_npcs=8, npc_health=2, max_ticks=50,
                       flags=4 | 16 | 32, item_drop_pct=60), (1, 1), 1000, 77),
 })
-# round 4: the StaircaseBot form's lean spans (greedy walks with no staircase
-# target, meet or episode end ahead) on grids large enough that whole waves
-# walk lean for many ticks: episodes ending inside a span, separation damage
-# (lean only while the depths agree), players on different depths
+# round 4: the StaircaseBot form on grids large enough that whole waves walk
+# greedily for many ticks (no staircase target or meet ahead): episodes ending
+# mid-walk, separation damage across depths, players on different depths
 PAIRED_CASES.update({
     "stairs_lean_spans": (dict(width=96, height=96, max_ticks=150), (2, 2), 256, 85),
     "stairs_lean_sep": (dict(width=96, height=96, max_ticks=120, flags=1, sep_period=4), (2, 2),
