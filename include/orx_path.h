@@ -14,6 +14,14 @@
  * orx_path_query reads it for one player of every game.  Nothing in the tick
  * changes: this is a definition over the tiles, not a game rule.
  *
+ * The same question about targets that move -- how many moves away is the
+ * other player, the nearest NPC, the nearest item, and which move gets there --
+ * has one more rule built in: the updater descends an entity that steps onto a
+ * free StaircaseDown (updater.py:205-206), so a walk that stays on its depth
+ * may start or end on a staircase tile but cannot cross one.  orx_path_rows
+ * computes that distance from arbitrary source cells (all of them: the pair
+ * table of a bank); orx_path_seek reads the table for one player of every game.
+ *
  * It is a header of its own so that orx.h's list of entry points stays what
  * it is; the conventions (caller-owned device pointers, asynchronous on the
  * caller's stream, ORX_OK or a negative code with orx_last_error) are orx.h's.
@@ -82,6 +90,74 @@ int orx_path_query(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t* 
                    int32_t player, int32_t radius,
                    int32_t* dist, int8_t* move, uint16_t* window,
                    int64_t n_games, void* stream);
+
+/* ---- walking distances between cells --------------------------------------
+ * Row i of `rows` (uint16 [n][W * H]) is the walking distance from flat cell
+ * cell[i] (= x * H + y) of layout layout[i] to every tile of that layout, in
+ * the field's cell format: ORX_PATH_WALL on Wall tiles, ORX_PATH_UNREACHABLE
+ * where there is no walk, else the number of moves of the shortest 4-connected
+ * path whose interior cells are all Ground; its two end cells may be Ground or
+ * StaircaseDown (two adjacent staircases are 1 apart; a staircase in a one-wide
+ * corridor cuts it).  The distance is symmetric and 0 from a cell that is not
+ * Wall to itself.  A source that is a Wall tile, or an index outside [0, L) or
+ * [0, W * H), seeds nothing: its row is ORX_PATH_WALL on the Wall tiles (of the
+ * layout index clamped into the bank) and ORX_PATH_UNREACHABLE elsewhere.
+ * Entities are not part of the graph.  bank_tiles and the three cfg fields
+ * are orx_path_field's, and so is every bank it accepts; layout and cell are
+ * device int32 [n].  The pair table pairs[l][s][c], uint16 [L][W * H][W * H],
+ * is this over every (l, s).  One launch, no host sync, one workgroup and one
+ * LDS plane per row.  ORX_EINVAL: a NULL pointer, n <= 0 or dimensions outside
+ * the above; ORX_EIO: the device refuses the LDS. */
+int orx_path_rows(const orx_cfg_t* cfg, const uint8_t* bank_tiles,
+                  const int32_t* layout, const int32_t* cell, uint16_t* rows,
+                  int64_t n, void* stream);
+
+/* The columns of orx_path_seek's rows, and its two negative distances. */
+#define ORX_SEEK_PLAYER 0   /* column: the other player */
+#define ORX_SEEK_NPC    1   /* the nearest NPC whose alive bit is set */
+#define ORX_SEEK_ITEM   2   /* the nearest floor item (ORX_EXT_ITEMS) */
+#define ORX_SEEK_COLS   4   /* a row; column 3 pads it */
+#define ORX_SEEK_UNREACHABLE (-1)
+#define ORX_SEEK_ABSENT      (-2)
+
+/* For `player` (0 / 1) of every game, on that player's depth: how far the
+ * targets of each column are along walkable cells, and the move that gets one
+ * step closer.  The other player is a target when it is on the viewer's
+ * depth, whatever its health; NPCs (every slot of n_npcs whose alive bit is
+ * set) and floor items (ORX_EXT_ITEMS) only when the viewer is on the NPCs'
+ * depth.  The distance between two cells:
+ *   a dungeon bank: pairs[p_layout[player]][target cell][own cell] (pairs: the
+ *     table orx_path_rows wrote for the state's bank_tiles; the layout index is
+ *     clamped to the bank);
+ *   EmptyDungeonGenerator (pairs is NULL and ignored): |dx| + |dy|, plus 2 when
+ *     the two cells share a row or column and the staircase (st_x, st_y)[player]
+ *     lies strictly between them -- exact, because the interior is at least
+ *     two cells wide each way.
+ * Outputs (each may be NULL, not all three), rows of ORX_SEEK_COLS columns:
+ *   dist   int32 [n_games][4], 16-byte aligned: the least distance over the
+ *          column's targets; ORX_SEEK_UNREACHABLE when none of them can be
+ *          reached; ORX_SEEK_ABSENT when the column has no target.  0 occurs: a
+ *          player can stand on an item it could not take.
+ *   target int16 [n_games][4], 8-byte aligned: the lowest slot attaining dist --
+ *          the NPC slot, the item slot, 1 - player for the other player; -1
+ *          when absent.
+ *   move   int8 [n_games][4], 4-byte aligned: the first of ORX_MOVE_UP, RIGHT,
+ *          DOWN, LEFT whose neighbour cell is at dist - 1 from that target; a
+ *          StaircaseDown neighbour counts only if it is the target's own cell
+ *          (a step onto any other descends).  ORX_MOVE_STAY when dist <= 0.
+ *          Entities are not part of the graph: a move onto a cell holding an
+ *          NPC or the other player is an attack, as handle_move resolves it.
+ *   Column 3 is ORX_SEEK_ABSENT, ORX_MOVE_STAY, -1.
+ * Reads the state, writes only its outputs; no host sync (it can be captured
+ * in a graph behind orx_env_step), no random words; nothing depends on
+ * status.  ORX_EINVAL: player not 0 / 1, three NULL outputs, a misaligned
+ * output, n_games <= 0, a configuration orx_validate_cfg refuses, a bank
+ * without pairs, p_layout or bank_tiles, or a NULL state pointer that is read
+ * (p_x, p_y, p_depth; st_x and st_y without a bank; npc_pos, npc_health and
+ * npc_alive with NPCs; item_pos and item_mask with items). */
+int orx_path_seek(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t* pairs,
+                  int32_t player, int32_t* dist, int8_t* move, int16_t* target,
+                  int64_t n_games, void* stream);
 
 /* The id of the sources this part of the library was built from: the first 16
  * hex digits of SHA-256(orx_path.hip || orx_path.h), as orx_build_id() is of

@@ -93,6 +93,8 @@ _PATH = {
     "orx_path_field": (_int, [_cfg, vp, vp, vp]),
     "orx_path_query": (_int, [_cfg, _st, vp, i32, i32, vp, vp, vp, i64, vp]),
     "orx_path_build_id": (_str, []),
+    "orx_path_rows": (_int, [_cfg, vp, vp, vp, vp, i64, vp]),
+    "orx_path_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, i64, vp]),
 }
 _MOVES = {
     "orx_moves": (_int, [_cfg, _st, i32, vp, vp, vp, i64, vp]),

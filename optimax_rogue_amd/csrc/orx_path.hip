@@ -34,7 +34,26 @@
 // coalesced gather), written transposed into the tile -- takes dist and move
 // from the tile's centre cells, and streams the tile's contiguous bytes out
 // 16 per lane.
+//
+// rows_kernel: the distance plane from an arbitrary source cell, one row of
+// the pair table per workgroup, grid-stride over the rows.  field_kernel's
+// plane layout, sweeps and stream-out (Plane, relax_plane, stream_plane) on
+// another graph: a walk that stays on its depth cannot cross a StaircaseDown (the
+// updater descends whoever steps on one), so the staircases are marked kStair
+// and left out of the relaxation -- "Ground plus the source" -- and a
+// staircase that is not the source takes 1 + the least of its reached
+// neighbours only while the plane is streamed out (it is never written back,
+// so two adjacent staircases cannot see each other's value).  Thousands of
+// rows are in flight where the field has L layouts, so a workgroup is sized
+// by the plane (kRowsPerThread entries per thread), not fixed at 1,024.
+//
+// seek_kernel: moves_kernel's shape -- one lane per game, 256 per workgroup,
+// no LDS.  A lane reads one table cell per target (row = the target's cell,
+// column = its own: the table is symmetric), keeps the least per column, and
+// reads the chosen target's row at its four neighbours for the move.
 // Plain C++ and vector stores only.
+#include <cstdlib>
+
 #include "../../include/orx_path.h"
 #include "orx_query.h"
 
@@ -148,6 +167,173 @@ __global__ __launch_bounds__(kFieldBlock) void field_kernel(const FieldArgs a) {
     }
     for (int c = head + (nvec << 3) + t; c < WH; c += nt) dst[c] = p[plane_index(a, c)];
     __syncthreads();  // (the next layout overwrites the plane)
+  }
+}
+
+// ---------------------------------------------------------------------------
+// the rows of the pair table
+// ---------------------------------------------------------------------------
+// A layout's plane in LDS: runs along the grid's longer axis, one Wall
+// sentinel between runs, before the first and after the last.
+struct Plane {
+  int32_t H, WH;
+  int32_t ylong;  // runs along y (H >= W), else along x
+  int32_t S;      // run stride: the longer side + 1
+  int32_t N;      // plane entries: (shorter side) * S + 1
+
+  static Plane of(int W, int H) {
+    Plane g;
+    g.H = H, g.WH = W * H;
+    g.ylong = H >= W ? 1 : 0;
+    g.S = (g.ylong ? H : W) + 1;
+    g.N = (g.ylong ? W : H) * g.S + 1;
+    return g;
+  }
+  size_t lds_bytes() const { return ((size_t)N * sizeof(uint16_t) + 15) & ~(size_t)15; }
+  __device__ __forceinline__ int at(int x, int y) const {
+    return ylong ? x * S + y + 1 : y * S + x + 1;
+  }
+  // plane index of flat tile index c = x * H + y
+  __device__ __forceinline__ int index(int c) const {
+    const int x = c / H;
+    return at(x, c - x * H);
+  }
+};
+
+// A staircase the walk may end on but not cross.  Below the sentinels and above every distance: a shortest path of
+// 0xFFFD moves needs as many open tiles in a row with Walls between its turns,
+// far more than the 65,536 tiles of the largest plane.
+constexpr uint32_t kStair = 0xFFFD;
+
+// Relaxes plane entries [lo, hi) of p, d = min(d, 1 + min(neighbours)), until a
+// workgroup-wide vote finds a whole sweep without a change.  Wall, kStair and 0
+// (a seed) keep their values; kStair and the sentinels never spread (m + 1 is
+// not below kFar).  field_kernel's sweep with one more value to leave alone;
+// the field keeps its own (sharing this one cost it 2.5 % of its time, measured).
+__device__ __forceinline__ void relax_plane(volatile uint16_t* p, int lo, int hi, int S, int N) {
+  auto open = [](uint32_t v) { return v != kWall && v != kStair && v != 0u; };
+  int changed;
+  do {
+    changed = 0;
+    uint32_t carry = lo > 0 ? p[lo - 1] : kWall;
+    for (int i = lo; i < hi; ++i) {  // forward: carry = the value at i - 1
+      uint32_t v = p[i];
+      if (open(v)) {
+        uint32_t m = carry;
+        const uint32_t nx = i + 1 < N ? p[i + 1] : kWall;
+        m = nx < m ? nx : m;
+        if (i >= S) { const uint32_t u = p[i - S]; m = u < m ? u : m; }
+        if (i + S < N) { const uint32_t u = p[i + S]; m = u < m ? u : m; }
+        if (m + 1u < v) {  // (v <= kFar, so m < kFar - 1: a sentinel never spreads)
+          v = m + 1u;
+          p[i] = (uint16_t)v;
+          changed = 1;
+        }
+      }
+      carry = v;
+    }
+    carry = hi < N ? p[hi] : kWall;
+    for (int i = hi - 1; i >= lo; --i) {  // backward: carry = the value at i + 1
+      uint32_t v = p[i];
+      if (open(v)) {
+        uint32_t m = carry;
+        const uint32_t pv = i > 0 ? p[i - 1] : kWall;
+        m = pv < m ? pv : m;
+        if (i >= S) { const uint32_t u = p[i - S]; m = u < m ? u : m; }
+        if (i + S < N) { const uint32_t u = p[i + S]; m = u < m ? u : m; }
+        if (m + 1u < v) {
+          v = m + 1u;
+          p[i] = (uint16_t)v;
+          changed = 1;
+        }
+      }
+      carry = v;
+    }
+  } while (__syncthreads_or(changed));
+}
+
+// The plane's W * H cells, value(plane index) each, in tile order to dst: 16
+// bytes per lane, uint16 head / tail where dst does not start or end 16-byte
+// aligned.
+template <typename Value>
+__device__ __forceinline__ void stream_plane(const Plane& g, uint16_t* dst, int t, int nt,
+                                             Value value) {
+  const int WH = g.WH;
+  int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 1);
+  head = head < WH ? head : WH;
+  const int nvec = (WH - head) >> 3;
+  for (int c = t; c < head; c += nt) dst[c] = (uint16_t)value(g.index(c));
+  uint4* vdst = reinterpret_cast<uint4*>(dst + head);
+  for (int v = t; v < nvec; v += nt) {
+    const int c0 = head + (v << 3);
+    int x = c0 / g.H, y = c0 - x * g.H;
+    uint32_t w[4];
+    for (int k = 0; k < 4; ++k) {
+      uint32_t pair = 0;
+      for (int h = 0; h < 2; ++h) {
+        pair |= (uint32_t)value(g.at(x, y)) << (16 * h);
+        if (++y == g.H) { y = 0; ++x; }
+      }
+      w[k] = pair;
+    }
+    vdst[v] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  for (int c = head + (nvec << 3) + t; c < WH; c += nt) dst[c] = (uint16_t)value(g.index(c));
+}
+
+constexpr int kRowsPerThread = 64;    // plane entries a thread sweeps (ORX_ROWS_PER_THREAD=n: n)
+constexpr int kRowsMaxGrid = 16384;                  // workgroups of one launch (grid-stride above)
+
+struct RowsArgs {
+  const uint8_t* tiles;
+  const int32_t *layout, *cell;
+  uint16_t* rows;
+  int64_t n;
+  int32_t L;
+  Plane g;
+};
+
+__global__ __launch_bounds__(kFieldBlock) void rows_kernel(const RowsArgs a) {
+  extern __shared__ uint4 smem[];
+  volatile uint16_t* p = reinterpret_cast<volatile uint16_t*>(smem);
+  const Plane g = a.g;
+  const int t = threadIdx.x, nt = blockDim.x;
+  const int S = g.S, N = g.N, WH = g.WH;
+  const int per = (N + nt - 1) / nt;
+  const int lo = t * per < N ? t * per : N, hi = lo + per < N ? lo + per : N;
+
+  for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
+    // 1. the sentinels and the tiles: Ground "not reached", the staircases
+    // kStair; then the source, if it is a cell of the bank and not a Wall
+    const int32_t lay = a.layout[r], c0 = a.cell[r];
+    const bool in_bank = lay >= 0 && lay < a.L && c0 >= 0 && c0 < WH;
+    for (int k = t * S; k < N; k += nt * S) p[k] = (uint16_t)kWall;
+    const uint8_t* src = a.tiles + (size_t)clamp_layout(lay, a.L) * (size_t)WH;
+    for (int c = t; c < WH; c += nt) {
+      const uint8_t tile = src[c];
+      p[g.index(c)] = (uint16_t)(tile == ORX_TILE_WALL ? kWall
+                                 : in_bank && c == c0 ? 0u
+                                 : tile == ORX_TILE_STAIRCASE_DOWN ? kStair : kFar);
+    }
+    __syncthreads();
+
+    // 2. relax over Ground plus the source
+    relax_plane(p, lo, hi, S, N);
+
+    // 3. the row to HBM; a staircase other than the source ends a walk from
+    // its nearest reached neighbour (the sentinels stop a step off a run; an
+    // index test one off the first or last run)
+    stream_plane(g, a.rows + (size_t)r * (size_t)WH, t, nt, [&](int i) -> uint32_t {
+      const uint32_t v = p[i];
+      if (v != kStair) return v;
+      uint32_t m = p[i - 1];
+      const uint32_t nx = p[i + 1];
+      m = nx < m ? nx : m;
+      if (i >= S) { const uint32_t u = p[i - S]; m = u < m ? u : m; }
+      if (i + S < N) { const uint32_t u = p[i + S]; m = u < m ? u : m; }
+      return m < kStair ? m + 1u : kFar;
+    });
+    __syncthreads();  // (the next row overwrites the plane)
   }
 }
 
@@ -305,6 +491,146 @@ __global__ __launch_bounds__(kBlock) void window_kernel(const PathArgs a) {
   stream_out(tile, a.window + (size_t)b0 * (size_t)VV, nb * VV, t);
 }
 
+// ---------------------------------------------------------------------------
+// seek: the walking distance and first move to the moving targets
+// ---------------------------------------------------------------------------
+struct SeekArgs {
+  const int32_t *p_x, *p_y, *p_depth, *st_x, *st_y;
+  const int16_t* p_layout;
+  const uint8_t* bank_tiles;
+  const uint16_t* npc_pos;
+  const uint32_t* npc_alive;
+  const uint16_t* item_pos;
+  const uint32_t* item_mask;
+  const uint16_t* pairs;
+  int32_t* dist;
+  int8_t* move;
+  int16_t* target;
+  int64_t B;
+  int32_t W, H, K, L, player, npc_depth, items;
+};
+
+constexpr uint32_t kNoPath = 0x7FFFFFFFu;  // a target that cannot be reached (above every distance)
+
+// One game's viewer: its cell, and the distances from it.
+struct Seeker {
+  int W, H, x, y, sx, sy;
+  const uint16_t* table;  // pairs[layout], or nullptr: the closed form
+  const uint8_t* tiles;   // bank_tiles[layout], with the table
+
+  __device__ __forceinline__ bool inside(int cx, int cy) const {
+    return (uint32_t)cx < (uint32_t)W && (uint32_t)cy < (uint32_t)H;
+  }
+  // the walking distance between cells (ax, ay) and (tx, ty), both in the
+  // grid; kNoPath where there is no walk (or a cell is Wall)
+  __device__ __forceinline__ uint32_t between(int ax, int ay, int tx, int ty) const {
+    if (table) {
+      const uint32_t v = table[(size_t)(tx * H + ty) * (size_t)(W * H) + (size_t)(ax * H + ay)];
+      return v >= kFar ? kNoPath : v;
+    }
+    // EmptyDungeonGenerator: border Wall; an open interior at least two cells
+    // wide, so only a staircase strictly between two cells of one row or
+    // column costs a detour, of two moves
+    if (ax < 1 || ax > W - 2 || ay < 1 || ay > H - 2 || tx < 1 || tx > W - 2 || ty < 1 || ty > H - 2)
+      return kNoPath;
+    const int dx = ax - tx, dy = ay - ty;
+    uint32_t d = (uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy));
+    if (dx == 0 && sx == ax && (ay < sy) != (ty < sy) && sy != ay && sy != ty) d += 2u;
+    if (dy == 0 && sy == ay && (ax < sx) != (tx < sx) && sx != ax && sx != tx) d += 2u;
+    return d;
+  }
+  __device__ __forceinline__ bool staircase(int cx, int cy) const {
+    return tiles ? tiles[cx * H + cy] == ORX_TILE_STAIRCASE_DOWN : (cx == sx && cy == sy);
+  }
+  // the first of Up, Right, Down, Left whose cell is at dist - 1 from the
+  // target; a staircase counts only as the target's own cell
+  __device__ __forceinline__ int32_t move_to(uint32_t dist, int tx, int ty) const {
+    if (dist == 0u || dist == kNoPath) return ORX_MOVE_STAY;
+    const int nx[4] = {x, x + 1, x, x - 1}, ny[4] = {y - 1, y, y + 1, y};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!inside(nx[j], ny[j])) continue;
+      if (between(nx[j], ny[j], tx, ty) != dist - 1u) continue;
+      if (staircase(nx[j], ny[j]) && !(nx[j] == tx && ny[j] == ty)) continue;
+      return ORX_MOVE_UP + j;
+    }
+    return ORX_MOVE_STAY;
+  }
+};
+
+// the least distance of a column and the lowest slot attaining it
+struct Nearest {
+  uint32_t dist = kNoPath;
+  int32_t slot = -1, tx = 0, ty = 0;
+  __device__ __forceinline__ void offer(const Seeker& s, int32_t k, int tx_, int ty_) {
+    const uint32_t d = s.inside(tx_, ty_) ? s.between(s.x, s.y, tx_, ty_) : kNoPath;
+    if (slot < 0 || d < dist) dist = d, slot = k, tx = tx_, ty = ty_;
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
+  const int64_t B = a.B;
+  const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (b >= B) return;
+  const int K = a.K;
+  const auto [me, ot] = player_rows(a.player, B, b);
+
+  Seeker s;
+  s.W = a.W, s.H = a.H;
+  s.x = a.p_x[me], s.y = a.p_y[me];
+  s.sx = s.sy = -1, s.table = nullptr, s.tiles = nullptr;
+  if (a.L > 0) {
+    const size_t lay = (size_t)layout_of(a, me), WH = (size_t)(a.W * a.H);
+    s.table = a.pairs + lay * WH * WH;
+    s.tiles = a.bank_tiles + lay * WH;
+  } else {
+    s.sx = a.st_x[me], s.sy = a.st_y[me];
+  }
+  const int32_t d = a.p_depth[me];
+  const bool here = s.inside(s.x, s.y);  // (a cell outside the grid has no targets)
+
+  Nearest col[3];
+  if (here && a.p_depth[ot] == d)
+    col[ORX_SEEK_PLAYER].offer(s, 1 - a.player, a.p_x[ot], a.p_y[ot]);
+  if (here && K > 0 && d == a.npc_depth) {
+    // positions are x | y << 8, as npc_pos / item_pos pack them
+    uint32_t alive = 0;
+    for (int k = 0; k < K; ++k) {
+      if ((k & 31) == 0) alive = a.npc_alive[(int64_t)(k >> 5) * B + b];
+      if (!((alive >> (k & 31)) & 1u)) continue;
+      const uint32_t pos = a.npc_pos[(int64_t)k * B + b];
+      col[ORX_SEEK_NPC].offer(s, k, (int)(pos & 0xFFu), (int)(pos >> 8));
+    }
+    if (a.items) {
+      const uint32_t on = a.item_mask[b];
+      for (int k = 0; on >> k && k < K; ++k) {
+        if (!((on >> k) & 1u)) continue;
+        const uint32_t pos = a.item_pos[(int64_t)k * B + b];
+        col[ORX_SEEK_ITEM].offer(s, k, (int)(pos & 0xFFu), (int)(pos >> 8));
+      }
+    }
+  }
+
+  uint32_t dist[4], move[4], target[4];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const Nearest& n = col[j];
+    dist[j] = (uint32_t)(n.slot < 0 ? ORX_SEEK_ABSENT
+                         : n.dist == kNoPath ? ORX_SEEK_UNREACHABLE : (int32_t)n.dist);
+    move[j] = (uint32_t)(n.slot < 0 ? ORX_MOVE_STAY : s.move_to(n.dist, n.tx, n.ty));
+    target[j] = (uint32_t)n.slot & 0xFFFFu;
+  }
+  dist[3] = (uint32_t)ORX_SEEK_ABSENT, move[3] = ORX_MOVE_STAY, target[3] = 0xFFFFu;
+
+  // a game's row of each output: one store
+  if (a.dist) reinterpret_cast<uint4*>(a.dist)[b] = make_uint4(dist[0], dist[1], dist[2], dist[3]);
+  if (a.move)
+    reinterpret_cast<uint32_t*>(a.move)[b] = move[0] | move[1] << 8 | move[2] << 16 | move[3] << 24;
+  if (a.target)
+    reinterpret_cast<uint2*>(a.target)[b] =
+        make_uint2(target[0] | target[1] << 16, target[2] | target[3] << 16);
+}
+
 }  // namespace orx_path_dev
 
 #ifndef ORX_PATH_BUILD_ID
@@ -388,4 +714,77 @@ extern "C" int orx_path_query(const orx_cfg_t* cfg, const orx_state_t* st, const
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   hipLaunchKernelGGL(window_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, a);
   return orx_dev::launch_status("orx_path_query");
+}
+
+extern "C" int orx_path_rows(const orx_cfg_t* cfg, const uint8_t* bank_tiles, const int32_t* layout,
+                             const int32_t* cell, uint16_t* rows, int64_t n, void* stream) {
+  using namespace orx_path_dev;
+  using orx_dev::fail;
+  if (!cfg) return fail(ORX_EINVAL, "cfg is NULL");
+  if (cfg->n_layouts < 1 || cfg->n_layouts > 32767)
+    return fail(ORX_EINVAL, "orx_path_rows: n_layouts must be in [1, 32767]");
+  if (cfg->width < 1 || cfg->height < 1 || (int64_t)cfg->width * cfg->height > 65536)
+    return fail(ORX_EINVAL, "orx_path_rows: a bank needs W, H >= 1 and W * H <= 65536");
+  if (!bank_tiles || !layout || !cell || !rows)
+    return fail(ORX_EINVAL, "orx_path_rows: bank_tiles, layout, cell or rows is NULL");
+  if (n <= 0) return fail(ORX_EINVAL, "orx_path_rows: n must be positive");
+
+  RowsArgs a;
+  a.tiles = bank_tiles, a.layout = layout, a.cell = cell, a.rows = rows;
+  a.n = n, a.L = cfg->n_layouts;
+  a.g = Plane::of(cfg->width, cfg->height);
+  const size_t lds = a.g.lds_bytes();
+  if (lds > (size_t)kDefaultLds &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(rows_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ORX_EIO, "orx_path_rows: the device refuses the LDS a layout's plane needs");
+  }
+  // kRowsPerThread plane entries per thread (tools/bench_seek.py measures
+  // others through the environment), whole waves, at most kFieldBlock
+  int per = kRowsPerThread;
+  if (const char* e = getenv("ORX_ROWS_PER_THREAD")) per = atoi(e) >= 1 ? atoi(e) : per;
+  int block = (((a.g.N + per - 1) / per + 63) / 64) * 64;
+  block = block > kFieldBlock ? kFieldBlock : block;
+  const unsigned grid = (unsigned)(n < kRowsMaxGrid ? n : kRowsMaxGrid);
+  hipLaunchKernelGGL(rows_kernel, dim3(grid), dim3((unsigned)block), lds, (hipStream_t)stream, a);
+  return orx_dev::launch_status("orx_path_rows");
+}
+
+extern "C" int orx_path_seek(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t* pairs,
+                             int32_t player, int32_t* dist, int8_t* move, int16_t* target,
+                             int64_t n_games, void* stream) {
+  using namespace orx_path_dev;
+  using orx_dev::fail;
+  int r;
+  if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_path_seek", player))) return r;
+  if (!dist && !move && !target)
+    return fail(ORX_EINVAL, "orx_path_seek: dist, move and target are all NULL");
+  if ((r = check_games("orx_path_seek", n_games))) return r;
+  // (a row is one vector store)
+  if ((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(move) & 3) ||
+      (reinterpret_cast<uintptr_t>(target) & 7))
+    return fail(ORX_EINVAL,
+                "orx_path_seek: dist must be 16-byte, move 4-byte and target 8-byte aligned");
+  if ((r = check_state(cfg, st, kStairsNoBank | kBank | kNpcs | kItems))) return r;
+  if (!st->p_depth) return fail(ORX_EINVAL, "a required state pointer is NULL");
+  if (cfg->n_layouts > 0 && !pairs)
+    return fail(ORX_EINVAL, "orx_path_seek: n_layouts > 0 needs pairs");
+
+  SeekArgs a;
+  a.p_x = st->p_x, a.p_y = st->p_y, a.p_depth = st->p_depth;
+  a.st_x = st->st_x, a.st_y = st->st_y;
+  a.p_layout = st->p_layout, a.bank_tiles = st->bank_tiles;
+  a.npc_pos = st->npc_pos, a.npc_alive = st->npc_alive;
+  a.item_pos = st->item_pos, a.item_mask = st->item_mask;
+  a.pairs = cfg->n_layouts > 0 ? pairs : nullptr;
+  a.dist = dist, a.move = move, a.target = target;
+  a.B = n_games;
+  a.W = cfg->width, a.H = cfg->height, a.K = cfg->n_npcs, a.L = cfg->n_layouts;
+  a.player = player;
+  a.npc_depth = npc_depth(cfg);
+  a.items = has_items(cfg) ? 1 : 0;
+  const unsigned grid = (unsigned)((n_games + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(seek_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
+  return orx_dev::launch_status("orx_path_seek");
 }

@@ -95,6 +95,16 @@ class DungeonBank:
             self._stair_field.setflags(write=False)
         return self._stair_field
 
+    def pair_field(self) -> np.ndarray:
+        """uint16 [L, W * H, W * H]: the walking distance between every two
+        cells of a layout, flat index x * H + y (``path.pair_field``: a walk
+        may start or end on a staircase but not cross one); computed once."""
+        if getattr(self, "_pair_field", None) is None:
+            from .path import pair_field
+            self._pair_field = pair_field(self.layouts)
+            self._pair_field.setflags(write=False)
+        return self._pair_field
+
     def unreachable_ground(self) -> np.ndarray:
         """int64 [L]: per layout, the Ground tiles from which no staircase can
         be reached -- a player spawned on one can only wait for

@@ -120,6 +120,7 @@ class BatchedEngine:
         # player's layout index; all NULL for EmptyDungeonGenerator
         self.bank = None
         self._stair_field = None   # (the bank's distance field: made by the first path())
+        self._pair_field = None    # (the bank's pair table: made by the first seek())
         if cfg.layouts is not None:
             from .dungeons import DungeonBank
             bank = DungeonBank(cfg.layouts)
@@ -544,6 +545,69 @@ class BatchedEngine:
         self._call("orx_path_query", _ptr(field), int(player), int(radius or 0), _ptr(outs[0]),
                    _ptr(outs[1]), _ptr(outs[2]) if radius is not None else None, self.B,
                    self._stream())
+        return tuple(outs)
+
+    # the largest pair table ``pair_field`` builds: 2 * L * (W * H)^2 bytes
+    PAIR_FIELD_MAX_BYTES = 1 << 30
+
+    @property
+    def pair_field(self):
+        """The bank's pair table on the device, uint16 [L, W * H, W * H]: the
+        walking distance between every two cells of a layout (orx_path_rows
+        over every source, include/orx_path.h; ``DungeonBank.pair_field`` is
+        its host twin), built by one launch at the first use.  None without a
+        bank; a table above ``PAIR_FIELD_MAX_BYTES`` is refused."""
+        if self.bank is None:
+            return None
+        if self._pair_field is None:
+            self._require("orx_path_rows")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the pair table is built at the first seek() call: "
+                                   "call seek() (or read pair_field) once before capturing")
+            L, WH = len(self.bank), int(self.cfg.width) * int(self.cfg.height)
+            nbytes = 2 * L * WH * WH
+            if nbytes > self.PAIR_FIELD_MAX_BYTES:
+                raise ValueError(f"the pair table of {L} layouts of {self.cfg.width} x "
+                                 f"{self.cfg.height} tiles needs {nbytes} bytes "
+                                 f"({nbytes / 2**20:.0f} MiB), above PAIR_FIELD_MAX_BYTES = "
+                                 f"{self.PAIR_FIELD_MAX_BYTES}")
+            cells = torch.arange(L * WH, dtype=torch.int32, device=self.device)
+            layout, cell = cells // WH, cells % WH
+            pairs = torch.empty((L, WH, WH), dtype=torch.uint16, device=self.device)
+            with torch.cuda.device(self.device):
+                code = self.lib.orx_path_rows(self._pcfg, _ptr(self.bank_tiles), _ptr(layout),
+                                              _ptr(cell), _ptr(pairs), L * WH, self._stream())
+            _lib.check("orx_path_rows", code)
+            self._pair_field = pairs
+        return self._pair_field
+
+    def seek(self, player: int = 0, out=None):
+        """orx_path_seek (include/orx_path.h): how many moves ``player`` (0 /
+        1) of every game is from the other player, the nearest live NPC and
+        the nearest floor item along walkable cells of its depth, and the move
+        that gets it one step closer.  Returns ``(dist, move, target)``: int32,
+        int8 and int16 [n_games, SEEK_COLS = 4], columns SEEK_PLAYER, SEEK_NPC,
+        SEEK_ITEM and one of padding.  ``dist`` is SEEK_UNREACHABLE (-1) where
+        no target of the column can be reached and SEEK_ABSENT (-2) where it
+        has none; ``target`` the slot of the nearest (-1: none); ``move`` the
+        first of Up, Right, Down, Left that is one step closer to it, Stay
+        when ``dist <= 0``.  A walk may start or end on a staircase but not
+        cross one; entities are not obstacles (a move onto one is an attack).
+        One launch on the current stream from the resident state, no host
+        sync, no state change, no random words; with a bank the first call
+        also builds ``pair_field``.  ``out``: a ``(dist, move, target)`` tuple
+        of tensors written and returned instead of fresh ones.  The host
+        reference is ``path.seek(self.snapshot(), ...)``."""
+        from .path import SEEK_COLS
+        from .query import check_player
+        check_player(player)
+        self._require("orx_path_seek")
+        shape = (self.B, SEEK_COLS)
+        outs = self._outs(out, [(torch.int32, shape), (torch.int8, shape), (torch.int16, shape)],
+                          "(dist, move, target)", align=16, distinct=("dist", "move", "target"))
+        pairs = self.pair_field
+        self._call("orx_path_seek", _ptr(pairs), int(player), _ptr(outs[0]), _ptr(outs[1]),
+                   _ptr(outs[2]), self.B, self._stream())
         return tuple(outs)
 
     def moves(self, player: int = 0, out=None):

@@ -19,18 +19,28 @@ built library).
 One cell of a field (uint16): 0 on a StaircaseDown, else the number of moves
 to the nearest one, ``PATH_WALL`` on a Wall tile or outside the grid,
 ``PATH_UNREACHABLE`` on a tile that is not Wall but has no walkable path.
+
+``source_rows`` / ``pair_field`` and ``seek`` are the same for targets that
+move (``orx_path_rows`` / ``orx_path_seek``): the walking distance between two
+cells, and from a player to the other player, the nearest NPC and the nearest
+item.  The updater descends an entity that steps onto a free StaircaseDown
+(updater.py:205-206), so a walk that stays on its depth may start or end on a
+staircase but not cross one: the interior cells of a path are all Ground.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from .enums import Move, Tile
-from .query import (MOVE_DELTAS, bank_at, check_player, check_radius, i64, inside_grid, tile_at,
-                    window_cells)
+from .query import (MOVE_DELTAS, bank_at, check_player, check_radius, i64, inside_grid, item_rows,
+                    npc_depth, npc_rows, tile_at, window_cells)
 
-# include/orx_path.h ORX_PATH_*
+# include/orx_path.h ORX_PATH_* and ORX_SEEK_*
 PATH_WALL = 0xFFFF
 PATH_UNREACHABLE = 0xFFFE
+SEEK_PLAYER, SEEK_NPC, SEEK_ITEM, SEEK_COLS = 0, 1, 2, 4
+SEEK_UNREACHABLE = -1
+SEEK_ABSENT = -2
 
 
 def check_path_args(player: int, radius=None, cfg=None) -> None:
@@ -147,3 +157,164 @@ def query(snap: dict, cfg, player: int, radius=None, bank=None):
     if radius is None:
         return dist, move
     return dist, move, value(*window_cells(px, py, int(radius))).astype(np.uint16)
+
+
+def source_rows(layouts, layout, cell) -> np.ndarray:
+    """uint16 [n, W * H]: row ``i`` is the walking distance from flat cell
+    ``cell[i]`` (= x * H + y) of layout ``layout[i]`` of ``layouts`` ([L, W, H]
+    or [W, H] Tile codes) to every tile of that layout: PATH_WALL on Wall
+    tiles, PATH_UNREACHABLE where there is no walk, else the moves of the
+    shortest path whose interior cells are all Ground (its end cells may be
+    staircases).  A source on a Wall, or an index outside the bank, seeds
+    nothing (its row shows the Walls of the layout index clamped into the
+    bank).  A frontier breadth-first search over all rows at once on "Ground
+    plus the source"; the other staircases then take 1 + the least of their
+    reached neighbours."""
+    a = np.asarray(layouts)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError("layouts must be [L, W, H] Tile codes")
+    L, W, H = a.shape
+    lay, cell = i64(layout).reshape(-1), i64(cell).reshape(-1)
+    if lay.shape != cell.shape:
+        raise ValueError("layout and cell must have one length")
+    n, P = len(lay), (W + 2) * (H + 2)
+    pad = np.full((L, W + 2, H + 2), int(Tile.Wall), np.uint8)
+    pad[:, 1:-1, 1:-1] = a
+    tiles = pad[np.clip(lay, 0, L - 1)].reshape(-1)          # [n * P]: every row's own copy
+    wall, stair = tiles == int(Tile.Wall), tiles == int(Tile.StaircaseDown)
+    ground = ~wall & ~stair
+    dist = np.full(n * P, -1, np.int32)                       # -1: not reached
+    ok = (lay >= 0) & (lay < L) & (cell >= 0) & (cell < W * H)
+    c = np.where(ok, cell, 0)
+    frontier = np.arange(n) * P + (c // H + 1) * (H + 2) + c % H + 1
+    frontier = frontier[ok & ~wall[frontier]]
+    dist[frontier] = 0
+    steps = np.array([-1, 1, -(H + 2), H + 2], np.int64)
+    d = 0
+    while len(frontier):
+        d += 1
+        nxt = (frontier[:, None] + steps[None, :]).reshape(-1)
+        nxt = nxt[ground[nxt] & (dist[nxt] < 0)]
+        frontier = np.unique(nxt)
+        dist[frontier] = d
+    # a staircase that is not the source: one move from its nearest reached neighbour
+    plane = dist.reshape(n, W + 2, H + 2)
+    far = np.int32(PATH_UNREACHABLE)
+    seen = np.where(plane < 0, far, plane)
+    near = np.full_like(plane, far)
+    near[:, 1:-1, 1:-1] = np.minimum(np.minimum(seen[:, :-2, 1:-1], seen[:, 2:, 1:-1]),
+                                     np.minimum(seen[:, 1:-1, :-2], seen[:, 1:-1, 2:]))
+    end = stair.reshape(plane.shape) & (plane < 0) & (near < far)
+    out = np.where(wall.reshape(plane.shape), PATH_WALL, np.where(end, near + 1, seen))
+    return np.ascontiguousarray(out[:, 1:-1, 1:-1].reshape(n, W * H).astype(np.uint16))
+
+
+def pair_field(layouts) -> np.ndarray:
+    """uint16 [L, W * H, W * H]: ``pairs[l, s, c]`` is the walking distance
+    between flat cells ``s`` and ``c`` of layout ``l`` -- ``source_rows`` over
+    every source of every layout, symmetric in ``s`` and ``c``."""
+    a = np.asarray(layouts)
+    if a.ndim == 2:
+        a = a[None]
+    L, W, H = a.shape
+    cells = np.arange(W * H)
+    return np.stack([source_rows(a, np.full(W * H, l), cells) for l in range(L)])
+
+
+def room_distance(cfg, sx, sy, ax, ay, bx, by) -> np.ndarray:
+    """int64: the walking distance between cells (ax, ay) and (bx, by) of
+    EmptyDungeonGenerator's dungeon with its staircase at (sx, sy) (arrays
+    that broadcast): |dx| + |dy|, plus 2 when the two cells share a row or
+    column and the staircase lies strictly between them; PATH_WALL when either
+    cell is on the border or outside the grid.  Exact, because the interior is
+    at least two cells wide each way: a bent walk has two L-shaped routes and
+    the staircase can lie inside one of them only."""
+    W, H = int(cfg.width), int(cfg.height)
+    sx, sy, ax, ay, bx, by = np.broadcast_arrays(*(i64(v) for v in (sx, sy, ax, ay, bx, by)))
+    inner = lambda x, y: (x >= 1) & (x <= W - 2) & (y >= 1) & (y <= H - 2)
+    between = lambda s, a, b: ((a < s) & (s < b)) | ((b < s) & (s < a))
+    detour = ((ax == bx) & (sx == ax) & between(sy, ay, by)) \
+        | ((ay == by) & (sy == ay) & between(sx, ax, bx))
+    d = np.abs(ax - bx) + np.abs(ay - by) + 2 * detour
+    return np.where(inner(ax, ay) & inner(bx, by), d, PATH_WALL)
+
+
+def seek(snap: dict, cfg, player: int, bank=None):
+    """``(dist, move, target)``, int32, int8 and int16 [B, SEEK_COLS], of
+    ``player`` (0 / 1) of every game of a ``snapshot()``-shaped dict: column
+    SEEK_PLAYER the other player (a target when it is on the viewer's depth),
+    SEEK_NPC the NPCs whose alive bit is set and SEEK_ITEM the items on the
+    floor (both only when the viewer is on the NPCs' depth); column 3 pads.
+
+    dist    the least walking distance over the column's targets --
+            ``bank.pair_field()`` on the viewer's layout with a bank (made
+            from ``cfg.layouts`` when omitted), else ``room_distance``;
+            SEEK_UNREACHABLE when none can be reached, SEEK_ABSENT without a
+            target
+    target  the lowest slot attaining it (NPC slot, item slot, ``1 - player``
+            for the other player); -1 when absent
+    move    the first of Up, Right, Down, Left whose neighbour cell is at
+            ``dist - 1`` from that target -- a staircase neighbour only if it
+            is the target's own cell; Stay when ``dist <= 0``"""
+    check_player(player)
+    if bank is None and getattr(cfg, "layouts", None) is not None:
+        from .dungeons import DungeonBank
+        bank = DungeonBank(cfg.layouts)
+    p, q = int(player), 1 - int(player)
+    W, H, K = int(cfg.width), int(cfg.height), int(cfg.n_npcs)
+    px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
+    B = len(px)
+    depth = i64(snap["p_depth"][p])
+    if bank is None:
+        sx, sy = i64(snap["st_x"][p]), i64(snap["st_y"][p])
+    else:
+        pairs = bank.pair_field()
+        lay = np.clip(i64(snap["p_layout"][p]), 0, len(pairs) - 1)
+
+    def between(x, y, tx, ty):
+        """The distance between cells (x, y) and (tx, ty), int64 [..., B]."""
+        inside = inside_grid(cfg, x, y) & inside_grid(cfg, tx, ty)
+        if bank is None:
+            v = room_distance(cfg, sx, sy, x, y, tx, ty)
+        else:
+            flat = lambda u, v: np.clip(u, 0, W - 1) * H + np.clip(v, 0, H - 1)
+            v = pairs[lay, flat(tx, ty), flat(x, y)].astype(np.int64)
+        return np.where(inside, v, PATH_WALL)
+
+    def is_stair(x, y):
+        inside, tile = tile_at(cfg, snap, p, x, y, None if bank is None else bank.layouts)
+        return inside & (tile == int(Tile.StaircaseDown))
+
+    here = inside_grid(cfg, px, py)
+    on_npc_depth = here & (depth == npc_depth(cfg))
+    columns = [((here & (i64(snap["p_depth"][q]) == depth))[None],
+                i64(snap["p_x"][q])[None], i64(snap["p_y"][q])[None], np.array([q]))]
+    if K > 0:
+        alive, nx, ny, _ = npc_rows(snap, K)
+        columns.append((alive & on_npc_depth, nx, ny, np.arange(K)))
+        if snap.get("item_mask") is not None:
+            on, ix, iy, _ = item_rows(snap, K)
+            columns.append((on & on_npc_depth, ix, iy, np.arange(K)))
+    dist = np.full((B, SEEK_COLS), SEEK_ABSENT, np.int32)
+    move = np.full((B, SEEK_COLS), int(Move.Stay), np.int8)
+    target = np.full((B, SEEK_COLS), -1, np.int16)
+    games = np.arange(B)
+    for col, (present, tx, ty, slots) in enumerate(columns):
+        # absent above unreachable above every distance: argmin takes the lowest slot
+        v = between(px, py, tx, ty)
+        v = np.where(present, np.where(v >= PATH_UNREACHABLE, PATH_UNREACHABLE, v), PATH_WALL)
+        best = v.argmin(axis=0)
+        own, bx, by = v[best, games], tx[best, games], ty[best, games]
+        has = own != PATH_WALL
+        near = []
+        for _, dx, dy in MOVE_DELTAS:
+            x, y = px + dx, py + dy
+            near.append(np.where(is_stair(x, y) & ~((x == bx) & (y == by)), PATH_WALL,
+                                 between(x, y, bx, by)))
+        dist[:, col] = np.where(has, np.where(own == PATH_UNREACHABLE, SEEK_UNREACHABLE, own),
+                                SEEK_ABSENT)
+        move[:, col] = np.where(has, move_toward(own, *near), int(Move.Stay))
+        target[:, col] = np.where(has, slots[best], -1)
+    return dist, move, target

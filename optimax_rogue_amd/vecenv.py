@@ -168,6 +168,25 @@ class VecEnv:
         the first wall in its way."""
         return self.engine.path(player=player)[1]
 
+    def seek(self, player: int = 0, out=None):
+        """``(dist, move, target)`` of ``player`` (0: the learner) of every
+        game, [n_games, 4] each: how many moves away the other player, the
+        nearest NPC and the nearest floor item are along walkable cells, the
+        move that gets one step closer and the slot of the nearest
+        (``BatchedEngine.seek``; one launch, no host sync).  ``dist[:, 0]`` is
+        the usual pursuit potential: ``reward + c * (dist_before -
+        dist_after)`` on the steps where both are positive."""
+        return self.engine.seek(player=player, out=out)
+
+    def hunt_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games]: the move that takes ``player`` one step along a
+        shortest walk to the other player where one exists, else
+        ``stair_moves(player)`` -- a scripted pursuer on maps with interior
+        walls, ready as ``actions`` for ``step`` or as self-play's second
+        column.  Next to the other player the move is the attack."""
+        dist, move, _ = self.engine.seek(player=player)
+        return torch.where(dist[:, 0] > 0, move[:, 0], self.stair_moves(player))
+
     @staticmethod
     def outcome(before: torch.Tensor, after: torch.Tensor):
         """(reward, done) of a transition between two status tensors.  A game
