@@ -481,7 +481,9 @@ int orx_step_n_ex(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* act
                   uint64_t seed, int64_t game_offset, int32_t concurrency, void* stream);
 
 /* orx_step plus the update-event list of the tick: for game b,
- * events[(b * ORX_MAX_EVENTS + j) * 4 + 0..3], j < n_events[b], in the order
+ * events[(b * orx_max_events(cfg) + j) * 4 + 0..3], j < n_events[b] (the
+ * per-game stride is orx_max_events(cfg) records: ORX_MAX_EVENTS with Stay
+ * NPCs, more with moving ones -- size the buffer by it), in the order
  * Updater.update appends them to its result list (updater.py:133-145).
  * Steps that reset a game (autoreset) or reject an action record none. */
 int orx_step_events(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,

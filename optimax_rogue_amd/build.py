@@ -40,6 +40,9 @@ MOVES_SRC = os.path.join(PKG_DIR, "csrc", "orx_moves.hip")
 MOVES_HDR = os.path.join(ROOT, "include", "orx_moves.h")
 QUERY_HDR = os.path.join(PKG_DIR, "csrc", "orx_query.h")
 PLAN_HDR = os.path.join(PKG_DIR, "csrc", "orx_plan.h")   # the engine's launch plan (host side)
+# the tick with the NPCs' moves from the caller (orx_npc_*): defined in the
+# engine's source (it needs the moving-NPC tick), declared in a header of its own
+NPC_HDR = os.path.join(ROOT, "include", "orx_npc.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -69,6 +72,7 @@ PARTS = {
                  (PATH_SRC,)),
     "moves": Part("orx_moves_build_id", "ORX_MOVES_BUILD_ID", (MOVES_SRC, MOVES_HDR, QUERY_HDR),
                   (MOVES_SRC,)),
+    "npc": Part("orx_npc_build_id", "ORX_NPC_BUILD_ID", (NPC_HDR, SRC), ()),
 }
 SOURCES = [src for p in PARTS.values() for src in p.sources]   # (SRC first: _build_parts splits it)
 
@@ -106,26 +110,34 @@ def moves_id() -> str:
     return tree_ids()["moves"]
 
 
-def built_ids(path: str = OUT):
+def npc_id() -> str:
+    """What orx_npc_build_id() of a library built from these sources returns."""
+    return tree_ids()["npc"]
+
+
+def built_ids(path: str = OUT, every: bool = False):
     """``tree_ids``'s dict for the library at `path` ("" for a part it was built
     without; None if it cannot be loaded), read in one child process so this
-    one does not map a library that a later build replaces."""
+    one does not map a library that a later build replaces.  The parts
+    compiled from sources of their own; with ``every`` also those defined in
+    another part's source ("npc", whose id follows its header too)."""
+    parts = {name: p for name, p in PARTS.items() if every or p.sources}
     code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1])\n"
             "for f in (getattr(L,s,None) for s in sys.argv[2:]):\n"
             "    f and setattr(f,'restype',ctypes.c_char_p); print(f().decode() if f else '')")
-    cmd = [sys.executable, "-c", code, path] + [p.symbol for p in PARTS.values()]
+    cmd = [sys.executable, "-c", code, path] + [p.symbol for p in parts.values()]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=60)
     except (OSError, subprocess.SubprocessError):
         return None
     lines = out.stdout.split("\n")
-    if out.returncode != 0 or len(lines) <= len(PARTS):
+    if out.returncode != 0 or len(lines) <= len(parts):
         return None
-    return {name: line.strip() for name, line in zip(PARTS, lines)}
+    return {name: line.strip() for name, line in zip(parts, lines)}
 
 
 def _fresh(out: str, ids: dict) -> bool:
-    return os.path.exists(out) and built_ids(out) == ids
+    return os.path.exists(out) and built_ids(out, every=True) == ids
 
 
 def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (),
@@ -169,7 +181,7 @@ def _build_locked(out: str, ids: dict, defines, verbose: bool) -> str:
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
 # translation unit.  The other SOURCES (orx_view.hip, orx_path.hip and
 # orx_moves.hip: small) are one more object each, compiled last.
-NPARTS = 16
+NPARTS = 17
 
 
 def _build_parts(base, out, verbose=False, jobs=None):

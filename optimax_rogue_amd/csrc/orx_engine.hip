@@ -55,6 +55,7 @@
 #include <cstring>
 
 #include "../../include/orx.h"
+#include "../../include/orx_npc.h"
 #include "orx_plan.h"  // the launch plan (host side) and the constants it shares with the kernels
 
 // Split build (optimax_rogue_amd/build.py): this file is compiled ORX_NPARTS
@@ -2118,6 +2119,61 @@ struct NpcTurns<kDense> {
   __device__ __forceinline__ void mark(int k) { acted_[k >> 5] |= 1u << (k & 31); }
 };
 
+// Where a tick's NPC moves come from: the enemy AI (NoGiven: cfg.npc_policy),
+// or the caller's table (orx_npc_*, include/orx_npc.h): slot k's Move is the
+// byte p[k * B] (p: the tick's table [K][B] at this game).  A compile-time
+// choice -- the GIVEN instances of the moving-NPC kernels -- so the AI's
+// instances keep their code (DESIGN.md s4.3 "Given NPC moves").  Register NPCs:
+// load() reads every slot's byte up front, with the state words (as load_npcs:
+// no load behind a branch); dense NPCs: a byte is read where it is used.
+struct NoGiven {
+  static constexpr bool kOn = false;
+};
+template <int NCAP>
+struct GivenMoves {
+  static constexpr bool kOn = true;
+  const int8_t* p;
+  uint32_t B;
+  uint64_t mv;  // register NPCs: slot k's byte & 7 at bits 3 k
+  uint32_t ok;  // ... bit k: that byte is a Move (1..5)
+  __device__ __forceinline__ void load(const Cfg& c) {
+    mv = 0ull;
+    ok = 0u;
+    if constexpr (NCAP > 0 && NCAP != kDense) {
+      int32_t v[NCAP];
+#pragma unroll
+      for (int k = 0; k < NCAP; ++k) v[k] = p[(size_t)min(k, c.K - 1) * B];
+#pragma unroll
+      for (int k = 0; k < NCAP; ++k) {
+        mv |= (uint64_t)((uint32_t)v[k] & 7u) << (3 * k);
+        ok |= (v[k] >= ORX_MOVE_UP && v[k] <= ORX_MOVE_STAY) ? 1u << k : 0u;
+      }
+    }
+  }
+  // slot k's Move (an alive slot of a table that passed valid())
+  __device__ __forceinline__ int32_t get(int k) const {
+    if constexpr (NCAP == kDense) return p[(size_t)k * B];
+    else return (int32_t)((mv >> (3 * k)) & 7ull);
+  }
+  // every alive NPC's byte is a Move; dead slots' bytes are not looked at
+  __device__ __forceinline__ bool valid(const Cfg& c, const Npcs<NCAP>& npc) const {
+    if constexpr (NCAP == kDense) {
+      bool good = true;
+      for (int r = 0; r < (c.K + 31) >> 5; ++r) {
+        uint32_t a = npc.rows[(size_t)r * npc.B];
+        while (a) {
+          const int32_t v = p[(size_t)(32 * r + (int)__builtin_ctz(a)) * B];
+          a &= a - 1u;
+          good = good && v >= ORX_MOVE_UP && v <= ORX_MOVE_STAY;
+        }
+      }
+      return good;
+    } else {
+      return (npc.alive & ~ok & ((1u << c.K) - 1u)) == 0u;
+    }
+  }
+};
+
 // Register NPCs (moves decided): true iff no mover's target is a live NPC's
 // cell or another mover's target -- then the NPCs' handle_move calls commute
 // (updater.py:133-134: a move to a free cell, a hit on a player, or a
@@ -2387,13 +2443,13 @@ __device__ __forceinline__ void npc_sweep(const Cfg& c, Npcs<NCAP>& npc, M& m, D
   }
 }
 
-template <int NCAP, bool EV, bool GRID, class Src, class M, class BitsS, class BitsA>
+template <int NCAP, bool EV, bool GRID, class Src, class M, class BitsS, class BitsA, class G>
 __device__ __forceinline__ void tick_moving_body(const Cfg& c, Key key, Src& src, uint32_t game,
                                                  uint32_t ep, Player& p1, Player& p2,
                                                  Npcs<NCAP>& npc, M& m, int32_t& tick,
                                                  int32_t& status, bool& err, Deltas& dl,
                                                  Events<EV>& ev, int32_t& sep_start, BitsS& sh,
-                                                 BitsA& ai) {
+                                                 BitsA& ai, const G& gv) {
   ORX_MCYC_BEGIN(cy0);
   p1.heal = p2.heal = 0;
   calc_pos(p1.x, p1.y, p1.move, p1.tx, p1.ty);          // updater.py:89-98
@@ -2419,7 +2475,14 @@ __device__ __forceinline__ void tick_moving_body(const Cfg& c, Key key, Src& src
         while (a) {
           const int k = 32 * r + (int)__builtin_ctz(a);
           a &= a - 1u;
-          turns.set_move(k, decide_npc_move<GRID>(c, key, d, freeze, p1, p2, npc.get(k), ai, err));
+          if constexpr (G::kOn) {  // the caller's move behind the AI's guards
+            int32_t mv = ORX_MOVE_STAY;
+            if (d.present && !freeze) mv = npc_step_or_stay<GRID>(c, d, npc.get(k), gv.get(k));
+            turns.set_move(k, mv);
+          } else {
+            turns.set_move(k, decide_npc_move<GRID>(c, key, d, freeze, p1, p2, npc.get(k), ai,
+                                                    err));
+          }
           turns.set_slot(n++, k);
         }
       }
@@ -2427,7 +2490,21 @@ __device__ __forceinline__ void tick_moving_body(const Cfg& c, Key key, Src& src
 #pragma unroll
       for (int k = 0; k < NCAP; ++k)
         if (k < c.K && npc.is_alive(k)) turns.set_slot(n++, k);
-      if (c.npc_pol == ORX_NPC_RANDOM && d.present && !freeze) {
+      if constexpr (G::kOn) {
+        // the caller's moves behind the AI's guards: Stay on a depth without
+        // a dungeon or with a player next to a staircase tile, Stay where
+        // the target is blocked (no draw: the NPC stream is not touched)
+        if (d.present && !freeze) {
+#pragma unroll
+          for (int k = 0; k < NCAP; ++k)
+            if (k < c.K && npc.is_alive(k))
+              turns.set_move(k, npc_step_or_stay<GRID>(c, d, npc.get(k), gv.get(k)));
+        } else {
+#pragma unroll
+          for (int k = 0; k < NCAP; ++k)
+            if (k < c.K && npc.is_alive(k)) turns.set_move(k, ORX_MOVE_STAY);
+        }
+      } else if (c.npc_pol == ORX_NPC_RANDOM && d.present && !freeze) {
         // random.choice(list(Move)) per NPC as ONE per-lane loop over all the
         // NPCs' rejection draws (randbelow_bits unrolled by hand: same draws,
         // same give-up rule), so a wave iterates the max over its lanes of
@@ -2598,17 +2675,20 @@ __device__ __forceinline__ void tick_moving_body(const Cfg& c, Key key, Src& src
 // NPC shuffle -- from the tick block's word a and the SHUFFLE / NPC streams
 // (keyed), or from the game's CPython random in the reference's call order
 // (stock-seed mode).
-template <int NCAP, bool EV, bool GRID, class Src, class M>
+// gv: the NPCs' moves from the caller's table (GivenMoves) instead of the AI;
+// then nothing is drawn for them (keyed: the NPC stream is not opened;
+// stock-seed mode: no word between the two shuffles).
+template <int NCAP, bool EV, bool GRID, class Src, class M, class G = NoGiven>
 __device__ __forceinline__ void tick_moving(const Cfg& c, Key key, Src& src, uint32_t game,
                                             uint32_t ep, Player& p1, Player& p2,
                                             Npcs<NCAP>& npc, M& m, int32_t& tick,
                                             int32_t& status, bool& err, Deltas& dl,
                                             Events<EV>& ev, int32_t& sep_start,
-                                            const W4* tb = nullptr) {
+                                            const W4* tb = nullptr, const G& gv = G{}) {
   if constexpr (Src::kMt) {
     MtBits b{&src.py};
     tick_moving_body<NCAP, EV, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err, dl,
-                                     ev, sep_start, b, b);
+                                     ev, sep_start, b, b, gv);
   } else {
     // (blocks ahead: the shuffle of 8 NPCs takes ~5 words past the tick
     // block's word, the AI's choices of 8 ~2)
@@ -2621,9 +2701,9 @@ __device__ __forceinline__ void tick_moving(const Cfg& c, Key key, Src& src, uin
     ai.res = 0u;
     ai.nb = 0;
     ai.refill = true;
-    ai.s.init(game, ep, (uint32_t)tick, tag(PUR_NPC, 0), key);
+    if constexpr (!G::kOn) ai.s.init(game, ep, (uint32_t)tick, tag(PUR_NPC, 0), key);
     tick_moving_body<NCAP, EV, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err, dl,
-                                     ev, sep_start, sh, ai);
+                                     ev, sep_start, sh, ai, gv);
   }
 }
 
@@ -2943,11 +3023,15 @@ struct NoOut {
   __device__ __forceinline__ void operator()(const Player&, const Player&, int32_t, int32_t) {}
 };
 
-template <int NCAP, bool EV, bool GRID, bool EXT, bool MOV, class Src, class A, class O = NoOut>
+// gv (the GIVEN instances, orx_npc_*): the tick's NPC moves from the caller's
+// table.  A byte outside 1..5 in an alive NPC's slot refuses the tick like a
+// bad player action; a tick that resets the game does not look at the table.
+template <int NCAP, bool EV, bool GRID, bool EXT, bool MOV, class Src, class A, class O = NoOut,
+          class G = NoGiven>
 __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t& st, A get_action,
                                           uint32_t B, uint32_t i, Key key, uint32_t off,
                                           int32_t* __restrict__ events,
-                                          int32_t* __restrict__ n_events, O out = O{}) {
+                                          int32_t* __restrict__ n_events, O out = O{}, G gv = G{}) {
   constexpr bool kOut = !std::is_same<O, NoOut>::value;
   Cfg c = make_cfg(hc, st);
   if constexpr (!EXT) c.ext = 0;
@@ -2966,6 +3050,7 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
   src.open(st, c, B, i);  // (stock-seed mode: the streams' indices with the state words)
   load_npcs(st, c, B, i, npc);
   load_rpg(st, c, B, i, p1, p2, npc, items);
+  if constexpr (G::kOn) gv.load(c);
   if (c.ext & ORX_EXT_SEPARATION_DAMAGE) sep = st.sep_start[i];
   if constexpr (kOut) tb0 = tick_block(key, game, ep, tick);
   const uint16_t a = get_action(p1, p2, tick, ep, tb0);
@@ -2995,7 +3080,9 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
   }
   p1.move = (int8_t)(a & 0xFF);
   p2.move = (int8_t)(a >> 8);
-  if (!valid_move(c, p1.move) || !valid_move(c, p2.move)) {
+  bool refused = !valid_move(c, p1.move) || !valid_move(c, p2.move);
+  if constexpr (G::kOn) refused = refused || !gv.valid(c, npc);
+  if (refused) {
     st.status[i] = ORX_STATUS_BAD_ACTION;
     if (EV) n_events[i] = 0;
     out(p1, p2, tick, (int32_t)ORX_STATUS_BAD_ACTION);
@@ -3004,12 +3091,13 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
   src.episode(ep);
   NpcMem m{st.npc_pos, st.npc_health, B, i};
   Deltas dl = {0, 0, 0, 0, 0, 0};
-  const int32_t ev_cap = MOV ? max_events_for(c.npc_pol, c.K) : ORX_MAX_EVENTS;
+  const int32_t ev_cap = MOV ? max_events_for(G::kOn ? ORX_NPC_CHASE : c.npc_pol, c.K)
+                             : ORX_MAX_EVENTS;
   Events<EV> ev{EV ? events + (size_t)i * (size_t)ev_cap * 4 : nullptr, 0, ev_cap};
   bool err = false;
   if constexpr (MOV) {  // moving NPCs: the literal ordered tick draws its own shuffles
     tick_moving<NCAP, EV, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err, dl, ev,
-                                sep);
+                                sep, nullptr, gv);
     store_npc_cells(st, c, B, i, npc);
   } else {
     bool p1_first;  // the initiative (stock-seed mode: and the NPC shuffles' draws)
@@ -3033,20 +3121,29 @@ __device__ __forceinline__ void step_game(const orx_cfg_t& hc, const orx_state_t
 
 // MT: stock-seed mode -- the tick's draws from the game's own streams, which a
 // refused pair or a finished game without autoreset leaves as they are
-template <int NCAP, bool EV, bool GRID, bool EXT = true, bool MOV = false, bool MT = false>
+// GIVEN (with MOV; orx_npc_step): the NPCs' moves from npc_moves [K][B], which
+// the other instances do not read
+template <int NCAP, bool EV, bool GRID, bool EXT = true, bool MOV = false, bool MT = false,
+          bool GIVEN = false>
 __global__ void __launch_bounds__(256) step_kernel(orx_cfg_t hc, orx_state_t st,
                                                    const int8_t* __restrict__ actions, uint32_t B,
                                                    Key key, uint32_t off,
                                                    int32_t* __restrict__ events,
-                                                   int32_t* __restrict__ n_events) {
+                                                   int32_t* __restrict__ n_events,
+                                                   const int8_t* __restrict__ npc_moves) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
+  std::conditional_t<GIVEN, GivenMoves<NCAP>, NoGiven> gv{};
+  if constexpr (GIVEN) {
+    gv.p = npc_moves + i;
+    gv.B = B;
+  }
   step_game<NCAP, EV, GRID, EXT, MOV, std::conditional_t<MT, MtSrc, PhiloxSrc>>(
       hc, st,
       [&](const Player&, const Player&, int32_t, uint32_t, const W4&) {
         return reinterpret_cast<const uint16_t*>(actions)[i];
       },
-      B, i, key, off, events, n_events);
+      B, i, key, off, events, n_events, NoOut{}, gv);
 }
 
 // MT: stock-seed mode -- RandomBot's moves from the game's CPython stream
@@ -3111,13 +3208,14 @@ __global__ void __launch_bounds__(256) policy_kernel(orx_state_t st, int32_t pol
 #ifndef ORX_ENV_DIAG  // diagnostic builds: 1 no tick, 2 no observation rows
 #define ORX_ENV_DIAG 0
 #endif
-template <int NCAP, bool GRID, bool EXT, bool MOV = false>
+template <int NCAP, bool GRID, bool EXT, bool MOV = false, bool GIVEN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORX_ENV_WAVES)))
 env_step_kernel(
     orx_cfg_t hc, orx_state_t st, const void* __restrict__ actions, int32_t dsize, int32_t cols,
     int32_t pol2, int8_t* __restrict__ act, int32_t* __restrict__ obs, float* __restrict__ reward,
     uint8_t* __restrict__ done, int32_t* __restrict__ status_out, uint32_t* __restrict__ bad_count,
-    uint32_t B, Key key, uint32_t off, int32_t lds_rows, uint32_t lanes) {
+    uint32_t B, Key key, uint32_t off, int32_t lds_rows, uint32_t lanes,
+    const int8_t* __restrict__ npc_moves) {  // (GIVEN, orx_npc_env_step: the NPCs' moves [K][B])
   __shared__ __attribute__((aligned(16))) int32_t rows_lds[256 * ORX_OBS_FIELDS];
   // `lanes` games per wave (64, or 32: two half-full waves per SIMD at the
   // config batch, whose state loads then overlap the other wave's tick); a
@@ -3182,8 +3280,13 @@ env_step_kernel(
       pair = pack_actions(l1, l2);
       out(p1, p2, st.tick[i], before);
     } else {
+      std::conditional_t<GIVEN, GivenMoves<NCAP>, NoGiven> gv{};
+      if constexpr (GIVEN) {
+        gv.p = npc_moves + i;
+        gv.B = B;
+      }
       step_game<NCAP, false, GRID, EXT, MOV, PhiloxSrc>(hc, st, get_action, B, i, key, off,
-                                                        nullptr, nullptr, out);
+                                                        nullptr, nullptr, out, gv);
     }
     reinterpret_cast<uint16_t*>(act)[i] = pair;
   }
@@ -4774,11 +4877,14 @@ __global__ void __launch_bounds__(256) mt_seed_kernel(orx_state_t st, uint32_t B
 // leaves this tick's stores in flight -- with the row branch at run time the
 // compiler's wait at the loop head has to assume a path without stores and
 // drains them all every tick.
-template <int NCAP, bool GRID, int ROWS, bool MOV = false>
+// GIVEN (with MOV; orx_npc_step_n): step t's NPC moves from npc_moves
+// [n_ticks][K][B], indexed by the step, not by the game's tick.
+template <int NCAP, bool GRID, int ROWS, bool MOV = false, bool GIVEN = false>
 __device__ __forceinline__ void step_n_game(const orx_cfg_t& hc, const orx_state_t& st,
                                             const int8_t* __restrict__ actions, int32_t n_ticks,
                                             int32_t* __restrict__ obs, uint32_t B, uint32_t i,
-                                            Key key, uint32_t off) {
+                                            Key key, uint32_t off,
+                                            const int8_t* __restrict__ npc_moves = nullptr) {
   const Cfg c = make_cfg(hc, st);
   const uint32_t game = off + i;
   Player p1, p2;
@@ -4814,7 +4920,15 @@ __device__ __forceinline__ void step_n_game(const orx_cfg_t& hc, const orx_state
     if (status == ORX_IN_PROGRESS) {
       p1.move = a1;
       p2.move = a2;
-      if (!valid_move(c, a1) || !valid_move(c, a2)) {
+      std::conditional_t<GIVEN, GivenMoves<NCAP>, NoGiven> gv{};
+      bool refused = !valid_move(c, a1) || !valid_move(c, a2);
+      if constexpr (GIVEN) {
+        gv.p = npc_moves + (size_t)t * (size_t)c.K * B + i;
+        gv.B = B;
+        gv.load(c);
+        refused = refused || !gv.valid(c, npc);
+      }
+      if (refused) {
         status = ORX_STATUS_BAD_ACTION;
       } else {
         bool err = false;
@@ -4823,7 +4937,7 @@ __device__ __forceinline__ void step_n_game(const orx_cfg_t& hc, const orx_state
         if constexpr (MOV) {
           PhiloxSrc src{key, game, ep};
           tick_moving<NCAP, false, GRID>(c, key, src, game, ep, p1, p2, npc, m, tick, status, err,
-                                         dl, ev, sep);
+                                         dl, ev, sep, nullptr, gv);
           npc_dirty = true;
         } else {
           const bool p1_first = p1_first_draw(key, game, ep, tick, err);
@@ -4854,20 +4968,24 @@ __device__ __forceinline__ void step_n_game(const orx_cfg_t& hc, const orx_state
   flush_deltas(st, B, i, dl);
 }
 
-template <int NCAP, bool GRID, bool MOV = false>
+template <int NCAP, bool GRID, bool MOV = false, bool GIVEN = false>
 __global__ void __launch_bounds__(256) step_n_kernel(orx_cfg_t hc, orx_state_t st,
                                                      const int8_t* __restrict__ actions,
                                                      int32_t n_ticks, int32_t* __restrict__ obs,
                                                      uint32_t B, Key key, uint32_t off,
-                                                     int32_t fmt) {
+                                                     int32_t fmt,
+                                                     const int8_t* __restrict__ npc_moves) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
   if (obs == nullptr)  // (uniform)
-    step_n_game<NCAP, GRID, 0, MOV>(hc, st, actions, n_ticks, obs, B, i, key, off);
+    step_n_game<NCAP, GRID, 0, MOV, GIVEN>(hc, st, actions, n_ticks, obs, B, i, key, off,
+                                           npc_moves);
   else if (fmt == ORX_OBS_COMPACT)
-    step_n_game<NCAP, GRID, 2, MOV>(hc, st, actions, n_ticks, obs, B, i, key, off);
+    step_n_game<NCAP, GRID, 2, MOV, GIVEN>(hc, st, actions, n_ticks, obs, B, i, key, off,
+                                           npc_moves);
   else
-    step_n_game<NCAP, GRID, 1, MOV>(hc, st, actions, n_ticks, obs, B, i, key, off);
+    step_n_game<NCAP, GRID, 1, MOV, GIVEN>(hc, st, actions, n_ticks, obs, B, i, key, off,
+                                           npc_moves);
 }
 
 // orx_rollout, one lane per game, for stock-seed mode and for moving NPCs
@@ -5174,17 +5292,25 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
                                                            const uint8_t*, uint32_t, Key,       \
                                                            uint32_t);
 #define ORX_I_RESET(N, G) ORX_I_RESET_MT(N, G, false) ORX_I_RESET_MT(N, G, true)
-#define ORX_I_STEP_M(N, E, G, MOV, MT)                                                          \
-  ORX_INST template __global__ void step_kernel<N, E, G, true, MOV, MT>(                        \
-      orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*);
-#define ORX_I_STEP(N, E, G) ORX_I_STEP_M(N, E, G, false, false) ORX_I_STEP_M(N, E, G, false, true)
+#define ORX_I_STEP_M(N, E, G, MOV, MT, GV)                                                      \
+  ORX_INST template __global__ void step_kernel<N, E, G, true, MOV, MT, GV>(                    \
+      orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*,       \
+      const int8_t*);
+#define ORX_I_STEP(N, E, G)                                                                     \
+  ORX_I_STEP_M(N, E, G, false, false, false) ORX_I_STEP_M(N, E, G, false, true, false)
 #define ORX_I_STEP_REF(N)                                                                       \
   ORX_INST template __global__ void step_kernel<N, false, false, false>(                        \
-      orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*);
-#define ORX_I_ENV(N, G, X)                                                                      \
-  ORX_INST template __global__ void env_step_kernel<N, G, X>(                                   \
+      orx_cfg_t, orx_state_t, const int8_t*, uint32_t, Key, uint32_t, int32_t*, int32_t*,       \
+      const int8_t*);
+#define ORX_I_ENV_M(N, G, X, MOV, GV)                                                           \
+  ORX_INST template __global__ void env_step_kernel<N, G, X, MOV, GV>(                          \
       orx_cfg_t, orx_state_t, const void*, int32_t, int32_t, int32_t, int8_t*, int32_t*, float*, \
-      uint8_t*, int32_t*, uint32_t*, uint32_t, Key, uint32_t, int32_t, uint32_t);
+      uint8_t*, int32_t*, uint32_t*, uint32_t, Key, uint32_t, int32_t, uint32_t, const int8_t*);
+#define ORX_I_ENV(N, G, X) ORX_I_ENV_M(N, G, X, false, false)
+#define ORX_I_STEP_N_M(N, G, MOV, GV)                                                           \
+  ORX_INST template __global__ void step_n_kernel<N, G, MOV, GV>(                               \
+      orx_cfg_t, orx_state_t, const int8_t*, int32_t, int32_t*, uint32_t, Key, uint32_t,        \
+      int32_t, const int8_t*);
 #define ORX_I_PAIR(N, P, A, S, C, G)                                                            \
   ORX_INST template __global__ void pair_rollout_kernel<N, P, A, S, C, G>(                      \
       orx_cfg_t, orx_state_t, int32_t, int32_t*, int8_t*, uint32_t, Key, uint32_t, uint32_t,     \
@@ -5193,22 +5319,18 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
   ORX_INST template __global__ void rollout_kernel<N, P, G, A, C>(                              \
       orx_cfg_t, orx_state_t, int32_t, int32_t, int32_t, int32_t*, int8_t*, uint32_t, Key,      \
       uint32_t, uint32_t, uint32_t, uint32_t, int32_t);
-#define ORX_I_STEP_N(N, G)                                                                      \
-  ORX_INST template __global__ void step_n_kernel<N, G>(orx_cfg_t, orx_state_t, const int8_t*,  \
-                                                        int32_t, int32_t*, uint32_t, Key,       \
-                                                        uint32_t, int32_t);
+#define ORX_I_STEP_N(N, G) ORX_I_STEP_N_M(N, G, false, false)
 #define ORX_I_REPLAY(N, R, E)                                                                   \
   ORX_INST template __global__ void replay_kernel<N, R, E>(orx_cfg_t, orx_state_t,              \
                                                            const int8_t*, int32_t, int32_t*,    \
                                                            uint32_t, Key, uint32_t, uint32_t);
-#define ORX_I_MOV_STEP(N, E, G) ORX_I_STEP_M(N, E, G, true, false) ORX_I_STEP_M(N, E, G, true, true)
-#define ORX_I_MOV_NG(N, G)                                                                      \
-  ORX_INST template __global__ void step_n_kernel<N, G, true>(orx_cfg_t, orx_state_t,           \
-                                                              const int8_t*, int32_t, int32_t*, \
-                                                              uint32_t, Key, uint32_t, int32_t); \
-  ORX_INST template __global__ void env_step_kernel<N, G, true, true>(                          \
-      orx_cfg_t, orx_state_t, const void*, int32_t, int32_t, int32_t, int8_t*, int32_t*, float*, \
-      uint8_t*, int32_t*, uint32_t*, uint32_t, Key, uint32_t, int32_t, uint32_t);
+#define ORX_I_MOV_STEP(N, E, G)                                                                 \
+  ORX_I_STEP_M(N, E, G, true, false, false) ORX_I_STEP_M(N, E, G, true, true, false)
+#define ORX_I_MOV_NG(N, G) ORX_I_STEP_N_M(N, G, true, false) ORX_I_ENV_M(N, G, true, true, false)
+// the GIVEN instances (orx_npc_*): the moving-NPC lists once more
+#define ORX_I_NPC_STEP(N, E, G)                                                                 \
+  ORX_I_STEP_M(N, E, G, true, false, true) ORX_I_STEP_M(N, E, G, true, true, true)
+#define ORX_I_NPC_NG(N, G) ORX_I_STEP_N_M(N, G, true, true) ORX_I_ENV_M(N, G, true, true, true)
 #define ORX_I_LANE_ROLLOUT(N, G, MT, MOV)                                                       \
   ORX_INST template __global__ void lane_rollout_kernel<N, G, MT, MOV>(                         \
       orx_cfg_t, orx_state_t, int32_t, int32_t, int32_t, int32_t*, int8_t*, uint32_t, Key,      \
@@ -5223,7 +5345,8 @@ __global__ void __launch_bounds__(256) stairs_kernel(orx_cfg_t hc, orx_state_t s
 // the parts: 1-6 the paired rollouts (NCAP 0 / 8 / 16, halves A and B), 7-9
 // the one-lane rollouts per NCAP, 10 the dense rollouts and env_step, 11 the
 // step kernels, 12 the rest, 13 the mixed-bot paired rollouts, 14 the
-// moving-NPC kernels, 15 the paired replays; each costs a few tens of
+// moving-NPC kernels, 15 the paired replays, 16 the moving-NPC kernels that
+// take the NPCs' moves from the caller (orx_npc_*); each costs a few tens of
 // seconds of hipcc
 #define ORX_OWNS(k) (ORX_PART == 0 || ORX_PART == (k))
 #if ORX_OWNS(1)
@@ -5275,6 +5398,10 @@ ORX_PAIR_LIST_L(ORX_I_PAIR, 16)
 ORX_MOV_STEP_LIST(ORX_I_MOV_STEP)
 ORX_MOV_NG_LIST(ORX_I_MOV_NG)
 ORX_MOV_ROLLOUT_LIST(ORX_I_MOV_ROLLOUT)
+#endif
+#if ORX_OWNS(16)
+ORX_MOV_STEP_LIST(ORX_I_NPC_STEP)
+ORX_MOV_NG_LIST(ORX_I_NPC_NG)
 #endif
 #if ORX_OWNS(12)
 ORX_NG_LIST(ORX_I_RESET)
@@ -5587,11 +5714,26 @@ int orx_reset(const orx_cfg_t* cfg, const orx_state_t* st, const uint8_t* mask, 
   return fail(ORX_EIO, "orx_reset: no kernel instance for this configuration");
 }
 
+// What the orx_npc_* entry points ask of a checked cfg and of the table
+// (include/orx_npc.h): before any device call.
+static int check_given(const orx_cfg_t* cfg, const int8_t* npc_moves) {
+  if (cfg->n_npcs <= 0) return fail(ORX_EINVAL, "orx_npc_*: n_npcs must be > 0");
+  if (cfg->flags & ~(ORX_EXT_SEPARATION_DAMAGE | ORX_EXT_RANDOM_DOUBLE_DEATH))
+    return fail(ORX_EINVAL, "orx_npc_*: moving NPCs need flags within "
+                            "ORX_EXT_SEPARATION_DAMAGE | ORX_EXT_RANDOM_DOUBLE_DEATH");
+  if (!npc_moves) return fail(ORX_EINVAL, "npc_moves is NULL");
+  return ORX_OK;
+}
+
+// given: the NPCs' moves from npc_moves (orx_npc_step / orx_npc_step_events)
 static int launch_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
                        int32_t* events, int32_t* n_events, int64_t n_games, uint64_t seed,
-                       int64_t game_offset, void* stream, const char* name) {
+                       int64_t game_offset, void* stream, const char* name,
+                       const int8_t* npc_moves = nullptr, bool given = false) {
   int r;
-  if ((r = check_cfg(cfg)) || (r = check_sizes(n_games, game_offset))) return r;
+  if ((r = check_cfg(cfg)) || (given && (r = check_given(cfg, npc_moves))) ||
+      (r = check_sizes(n_games, game_offset)))
+    return r;
   if (n_games == 0) return ORX_OK;
   if ((r = check_state(cfg, st, true))) return r;
   if (!actions) return fail(ORX_EINVAL, "actions is NULL");
@@ -5603,15 +5745,20 @@ static int launch_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t
   const int nc = ncap_for(cfg->n_npcs);
   const bool grid = cfg->n_layouts > 0;
   const bool mt = cfg->rng == ORX_RNG_MT19937;
-#define ORX_STEP_ARGS B, s, *cfg, *st, actions, B, k, off, events, n_events
-#define ORX_STEP(NC, E, G, MOV)                                                                 \
+#define ORX_STEP_ARGS B, s, *cfg, *st, actions, B, k, off, events, n_events, npc_moves
+#define ORX_STEP(NC, E, G, MOV, GV)                                                             \
   if (nc == NC && ev == E && grid == G)                                                         \
-    return launch(name, mt ? step_kernel<NC, E, G, true, MOV, true>                             \
-                           : step_kernel<NC, E, G, true, MOV, false>, ORX_STEP_ARGS);
-#define ORX_STEP_MOV(NC, E, G) ORX_STEP(NC, E, G, true)
-#define ORX_STEP_STAY(NC, E, G) ORX_STEP(NC, E, G, false)
+    return launch(name, mt ? step_kernel<NC, E, G, true, MOV, true, GV>                         \
+                           : step_kernel<NC, E, G, true, MOV, false, GV>, ORX_STEP_ARGS);
+#define ORX_STEP_GIVEN(NC, E, G) ORX_STEP(NC, E, G, true, true)
+#define ORX_STEP_MOV(NC, E, G) ORX_STEP(NC, E, G, true, false)
+#define ORX_STEP_STAY(NC, E, G) ORX_STEP(NC, E, G, false, false)
 #define ORX_STEP_REF(NC)                                                                        \
   if (nc == NC) return launch(name, step_kernel<NC, false, false, false>, ORX_STEP_ARGS);
+  if (given) {  // the ordered tick with the caller's NPC moves, whatever cfg->npc_policy
+    ORX_MOV_STEP_LIST(ORX_STEP_GIVEN)
+    return fail(ORX_EIO, "orx_npc_step: no kernel instance for this configuration");
+  }
   if (moving_npcs(cfg)) {  // the ordered tick with the enemy AI
     ORX_MOV_STEP_LIST(ORX_STEP_MOV)
     return fail(ORX_EIO, "orx_step: no moving-NPC kernel instance for this configuration");
@@ -5623,6 +5770,7 @@ static int launch_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t
 #undef ORX_STEP_REF
 #undef ORX_STEP_STAY
 #undef ORX_STEP_MOV
+#undef ORX_STEP_GIVEN
 #undef ORX_STEP
 #undef ORX_STEP_ARGS
   return fail(ORX_EIO, "orx_step: no kernel instance for this configuration");
@@ -5650,12 +5798,16 @@ int orx_step_n(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* action
                        stream);
 }
 
-int orx_step_n_ex(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
-                  int32_t n_ticks, int32_t* obs, int32_t obs_format, int64_t n_games,
-                  uint64_t seed, int64_t game_offset, int32_t concurrency, void* stream) {
+// given: step t's NPC moves from npc_moves [n_ticks][K][B] (orx_npc_step_n)
+static int launch_step_n(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
+                         int32_t n_ticks, int32_t* obs, int32_t obs_format, int64_t n_games,
+                         uint64_t seed, int64_t game_offset, int32_t concurrency, void* stream,
+                         const int8_t* npc_moves, bool given) {
   int r;
   if (concurrency < 1) return fail(ORX_EINVAL, "concurrency must be >= 1");
-  if ((r = check_cfg(cfg)) || (r = check_sizes(n_games, game_offset))) return r;
+  if ((r = check_cfg(cfg)) || (given && (r = check_given(cfg, npc_moves))) ||
+      (r = check_sizes(n_games, game_offset)))
+    return r;
   if (n_ticks < 0) return fail(ORX_EINVAL, "n_ticks < 0");
   if (obs_format != ORX_OBS_INT32 && obs_format != ORX_OBS_COMPACT)
     return fail(ORX_EINVAL, "unknown obs_format");
@@ -5671,13 +5823,14 @@ int orx_step_n_ex(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* act
   const int nc = ncap_for(cfg->n_npcs);
   const bool grid = cfg->n_layouts > 0;
   const int rows = obs ? (obs_format == ORX_OBS_COMPACT ? 2 : 1) : 0;
-  const Plan p = plan_step_n(cfg, B, rows, (uint32_t)concurrency, read_env(), device());
-#define ORX_STEP_N(N, G, MOV)                                                                   \
+  const Plan p = plan_step_n(cfg, B, rows, (uint32_t)concurrency, read_env(), device(), given);
+#define ORX_STEP_N(N, G, MOV, GV)                                                               \
   if (nc == N && grid == G)                                                                     \
-    return launch("orx_step_n", step_n_kernel<N, G, MOV>, p, s, *cfg, *st, actions, n_ticks,    \
-                  obs, B, k, off, obs_format);
-#define ORX_STEP_N_MOV(N, G) ORX_STEP_N(N, G, true)
-#define ORX_STEP_N_STAY(N, G) ORX_STEP_N(N, G, false)
+    return launch("orx_step_n", step_n_kernel<N, G, MOV, GV>, p, s, *cfg, *st, actions,         \
+                  n_ticks, obs, B, k, off, obs_format, npc_moves);
+#define ORX_STEP_N_GIVEN(N, G) ORX_STEP_N(N, G, true, true)
+#define ORX_STEP_N_MOV(N, G) ORX_STEP_N(N, G, true, false)
+#define ORX_STEP_N_STAY(N, G) ORX_STEP_N(N, G, false, false)
 #define ORX_PAIR_LOG(N, P, A, S, C, G)                                                          \
   if (nc == N && (A == kStreamAux) == p.nt && C == (rows == 2))                                 \
     return launch("orx_step_n", pair_rollout_kernel<N, P, A, S, C, G>, p, s, *cfg, *st,         \
@@ -5688,7 +5841,11 @@ int orx_step_n_ex(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* act
                   B, k, off, p.lanes);
   switch (p.form) {
     case Form::kMoving:
-      ORX_MOV_NG_LIST(ORX_STEP_N_MOV)
+      if (given) {
+        ORX_MOV_NG_LIST(ORX_STEP_N_GIVEN)
+      } else {
+        ORX_MOV_NG_LIST(ORX_STEP_N_MOV)
+      }
       return fail(ORX_EIO, "orx_step_n: no moving-NPC kernel instance for this configuration");
     case Form::kPaired: {  // the rollout's paired tick on the logged moves
       int8_t* log = const_cast<int8_t*>(actions);  // (PM 6 reads it; the form never writes it)
@@ -5706,8 +5863,16 @@ int orx_step_n_ex(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* act
 #undef ORX_PAIR_LOG
 #undef ORX_STEP_N_STAY
 #undef ORX_STEP_N_MOV
+#undef ORX_STEP_N_GIVEN
 #undef ORX_STEP_N
   return fail(ORX_EIO, "orx_step_n: no kernel instance for this configuration");
+}
+
+int orx_step_n_ex(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
+                  int32_t n_ticks, int32_t* obs, int32_t obs_format, int64_t n_games,
+                  uint64_t seed, int64_t game_offset, int32_t concurrency, void* stream) {
+  return launch_step_n(cfg, st, actions, n_ticks, obs, obs_format, n_games, seed, game_offset,
+                       concurrency, stream, nullptr, false);
 }
 
 int orx_policy(const orx_cfg_t* cfg, const orx_state_t* st, int32_t policy_p1, int32_t policy_p2,
@@ -5741,14 +5906,16 @@ int orx_env_step_args(const orx_env_step_args_t* a) {
                          a->bad_actions, a->n_games, a->seed, a->game_offset, a->stream);
 }
 
-int orx_env_step_ex(const orx_cfg_t* cfg, const orx_state_t* st, const void* actions,
-                    int32_t action_bytes, int32_t action_cols, int32_t policy_p2, int8_t* act,
-                    int32_t* obs, float* reward, uint8_t* done, int32_t* status,
-                    uint32_t* bad_actions, int64_t n_games, uint64_t seed, int64_t game_offset,
-                    void* stream) {
+// given: the NPCs' moves from npc_moves [K][B] (orx_npc_env_step)
+static int launch_env_step(const orx_cfg_t* cfg, const orx_state_t* st, const void* actions,
+                           int32_t action_bytes, int32_t action_cols, int32_t policy_p2,
+                           int8_t* act, int32_t* obs, float* reward, uint8_t* done,
+                           int32_t* status, uint32_t* bad_actions, int64_t n_games, uint64_t seed,
+                           int64_t game_offset, void* stream, const int8_t* npc_moves,
+                           bool given) {
   int r;
-  if ((r = check_cfg(cfg)) || (r = check_sizes(n_games, game_offset)) ||
-      (r = check_policy(policy_p2)))
+  if ((r = check_cfg(cfg)) || (given && (r = check_given(cfg, npc_moves))) ||
+      (r = check_sizes(n_games, game_offset)) || (r = check_policy(policy_p2)))
     return r;
   if (action_bytes != 1 && action_bytes != 2 && action_bytes != 4 && action_bytes != 8)
     return fail(ORX_EINVAL, "action_bytes must be 1, 2, 4 or 8");
@@ -5768,15 +5935,20 @@ int orx_env_step_ex(const orx_cfg_t* cfg, const orx_state_t* st, const void* act
   const Key k = make_key(seed);
   const int nc = ncap_for(cfg->n_npcs);
   const bool grid = cfg->n_layouts > 0;
-  const Plan p = plan_env_step(cfg, B, ((uintptr_t)obs & 15u) == 0, read_env());
+  const Plan p = plan_env_step(cfg, B, ((uintptr_t)obs & 15u) == 0, read_env(), given);
   const int32_t lds_rows = p.lds_rows ? 1 : 0;
-#define ORX_ENV(N, G, X, MOV)                                                                   \
+#define ORX_ENV(N, G, X, MOV, GV)                                                               \
   if (nc == N && grid == G && (cfg->flags == 0 || X))                                           \
-    return launch("orx_env_step", env_step_kernel<N, G, X, MOV>, p, s, *cfg, *st, actions,      \
+    return launch("orx_env_step", env_step_kernel<N, G, X, MOV, GV>, p, s, *cfg, *st, actions,  \
                   action_bytes, action_cols, policy_p2, act, obs, reward, done, status,         \
-                  bad_actions, B, k, off, lds_rows, p.lanes);
-#define ORX_ENV_MOV(N, G) ORX_ENV(N, G, true, true)
-#define ORX_ENV_STAY(N, G, X) ORX_ENV(N, G, X, false)
+                  bad_actions, B, k, off, lds_rows, p.lanes, npc_moves);
+#define ORX_ENV_GIVEN(N, G) ORX_ENV(N, G, true, true, true)
+#define ORX_ENV_MOV(N, G) ORX_ENV(N, G, true, true, false)
+#define ORX_ENV_STAY(N, G, X) ORX_ENV(N, G, X, false, false)
+  if (p.form == Form::kMoving && given) {
+    ORX_MOV_NG_LIST(ORX_ENV_GIVEN)
+    return fail(ORX_EIO, "orx_npc_env_step: no kernel instance for this configuration");
+  }
   if (p.form == Form::kMoving) {
     ORX_MOV_NG_LIST(ORX_ENV_MOV)
     return fail(ORX_EIO, "orx_env_step: no moving-NPC kernel instance for this configuration");
@@ -5784,8 +5956,64 @@ int orx_env_step_ex(const orx_cfg_t* cfg, const orx_state_t* st, const void* act
   ORX_ENV_LIST(ORX_ENV_STAY)
 #undef ORX_ENV_STAY
 #undef ORX_ENV_MOV
+#undef ORX_ENV_GIVEN
 #undef ORX_ENV
   return fail(ORX_EIO, "orx_env_step: no kernel instance for this configuration");
+}
+
+int orx_env_step_ex(const orx_cfg_t* cfg, const orx_state_t* st, const void* actions,
+                    int32_t action_bytes, int32_t action_cols, int32_t policy_p2, int8_t* act,
+                    int32_t* obs, float* reward, uint8_t* done, int32_t* status,
+                    uint32_t* bad_actions, int64_t n_games, uint64_t seed, int64_t game_offset,
+                    void* stream) {
+  return launch_env_step(cfg, st, actions, action_bytes, action_cols, policy_p2, act, obs, reward,
+                         done, status, bad_actions, n_games, seed, game_offset, stream, nullptr,
+                         false);
+}
+
+// ---- include/orx_npc.h: the tick with the NPCs' moves from the caller ----
+#ifndef ORX_NPC_BUILD_ID
+#define ORX_NPC_BUILD_ID "unknown"
+#endif
+const char* orx_npc_build_id(void) { return ORX_NPC_BUILD_ID; }
+
+int orx_npc_max_events(const orx_cfg_t* cfg) {
+  int r;
+  static const int8_t kSome = 0;  // (no table to check here)
+  if ((r = check_cfg(cfg)) || (r = check_given(cfg, &kSome))) return r;
+  return max_events_for(ORX_NPC_CHASE, cfg->n_npcs);
+}
+
+int orx_npc_step(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
+                 const int8_t* npc_moves, int64_t n_games, uint64_t seed, int64_t game_offset,
+                 void* stream) {
+  return launch_step(cfg, st, actions, nullptr, nullptr, n_games, seed, game_offset, stream,
+                     "orx_npc_step", npc_moves, true);
+}
+
+int orx_npc_step_events(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
+                        const int8_t* npc_moves, int32_t* events, int32_t* n_events,
+                        int64_t n_games, uint64_t seed, int64_t game_offset, void* stream) {
+  if (n_games > 0 && (!events || !n_events))
+    return fail(ORX_EINVAL, "orx_npc_step_events needs events and n_events");
+  return launch_step(cfg, st, actions, events, n_events, n_games, seed, game_offset, stream,
+                     "orx_npc_step_events", npc_moves, true);
+}
+
+int orx_npc_step_n(const orx_cfg_t* cfg, const orx_state_t* st, const int8_t* actions,
+                   const int8_t* npc_moves, int32_t n_ticks, int32_t* obs, int32_t obs_format,
+                   int64_t n_games, uint64_t seed, int64_t game_offset, int32_t concurrency,
+                   void* stream) {
+  return launch_step_n(cfg, st, actions, n_ticks, obs, obs_format, n_games, seed, game_offset,
+                       concurrency, stream, npc_moves, true);
+}
+
+int orx_npc_env_step(const orx_env_step_args_t* a, const int8_t* npc_moves) {
+  if (!a) return fail(ORX_EINVAL, "args is NULL");
+  return launch_env_step(a->cfg, a->st, a->actions, a->action_bytes, a->action_cols,
+                         a->policy_p2, a->act, a->obs, a->reward, a->done, a->status,
+                         a->bad_actions, a->n_games, a->seed, a->game_offset, a->stream,
+                         npc_moves, true);
 }
 
 int orx_rollout(const orx_cfg_t* cfg, const orx_state_t* st, int32_t policy_p1, int32_t policy_p2,

@@ -35,9 +35,11 @@ inline int ncap_for(int K) {
   return K == 0 ? 0 : K <= 8 ? 8 : K <= ORX_MAX_REG_NPCS ? 16 : kDense;
 }
 
-// The moving-NPC kernels serve this configuration (NPCs that move)
-inline bool moving_npcs(const orx_cfg_t* c) {
-  return c->npc_policy != ORX_NPC_STAY && c->n_npcs > 0;
+// The moving-NPC kernels serve this configuration (NPCs that move) -- and,
+// whatever its npc_policy, every call that brings the NPCs' moves with it
+// (given_moves: the orx_npc_* entry points, include/orx_npc.h)
+inline bool moving_npcs(const orx_cfg_t* c, bool given_moves = false) {
+  return (c->npc_policy != ORX_NPC_STAY || given_moves) && c->n_npcs > 0;
 }
 
 // What the plan needs of the device (the engine fills it from its per-device
@@ -288,9 +290,9 @@ inline Plan plan_rollout(const RolloutRequest& q, const Env& env, const Device& 
 // profiles/r06_v3 / r06_v4 ab_replay_paired.jsonl), else one lane per game
 // at the one-lane rollout's games per wave.
 inline Plan plan_step_n(const orx_cfg_t* cfg, uint32_t B, int rows, uint32_t concurrency,
-                        const Env& env, const Device& dev) {
+                        const Env& env, const Device& dev, bool given_moves = false) {
   Plan p{};
-  p.form = moving_npcs(cfg) ? Form::kMoving : Form::kGeneric;
+  p.form = moving_npcs(cfg, given_moves) ? Form::kMoving : Form::kGeneric;
   p.lanes = 64;
   p.nt = true;
   p.threads = kBlock;
@@ -315,9 +317,10 @@ inline Plan plan_step_n(const orx_cfg_t* cfg, uint32_t B, int rows, uint32_t con
 // The plan of an orx_env_step launch: 64 games per wave (32 measured no
 // better); the rows through LDS and 16-byte stores when obs is 16-byte
 // aligned (a torch allocation is; a view may not be: then direct stores).
-inline Plan plan_env_step(const orx_cfg_t* cfg, uint32_t B, bool obs_aligned, const Env& env) {
+inline Plan plan_env_step(const orx_cfg_t* cfg, uint32_t B, bool obs_aligned, const Env& env,
+                          bool given_moves = false) {
   Plan p{};
-  p.form = moving_npcs(cfg) ? Form::kMoving : Form::kGeneric;
+  p.form = moving_npcs(cfg, given_moves) ? Form::kMoving : Form::kGeneric;
   p.lanes = env.env_lanes;
   p.nt = true;
   p.threads = kBlock;

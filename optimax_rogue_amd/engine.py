@@ -299,16 +299,26 @@ class BatchedEngine:
             m8 = mask.to(device=self.device, dtype=torch.uint8).contiguous()
         self._call("orx_reset", _ptr(m8), self.B, self.seed, self.game_offset, self._stream())
 
-    def step(self, actions: Optional[torch.Tensor] = None, events: bool = False):
+    def step(self, actions: Optional[torch.Tensor] = None, events: bool = False,
+             npc_moves: Optional[torch.Tensor] = None):
         """Updater.update for every game: actions[b] = (player 1, player 2) Move
         values.  Returns the status tensor (UpdateResult codes, asynchronous);
         with ``events=True`` returns ``(status, events, n_events)``: the tick's
         update-event records int32 [n_games, max_events(), 4] and their counts
         (include/orx.h ORX_EV_*), in the reference's GameStateUpdate order;
         both buffers belong to the engine and are overwritten by the next
-        ``step(events=True)``."""
+        ``step(events=True)``.
+
+        ``npc_moves`` (int8 [n_npcs, n_games], slot-major: row k is NPC iden 3
+        + k) plays the tick with these NPC moves instead of cfg.npc_policy's
+        (orx_npc_step, include/orx_npc.h: the reference's decide_npc_move hook
+        as a table; the AI's guards apply, a byte outside 1..5 of a live NPC
+        stops that game with STATUS_BAD_ACTION); its event records are [n_games,
+        max_events(given=True), 4], in a buffer of their own."""
         a = self.actions if actions is None else actions
         self._check_actions(a, "actions")
+        if npc_moves is not None:
+            return self._step_given(a, events, npc_moves)
         if not events:
             self._call("orx_step", _ptr(a), self.B, self.seed, self.game_offset, self._stream())
             return self.status
@@ -320,26 +330,80 @@ class BatchedEngine:
                    self.game_offset, self._stream())
         return self.status, self._ev, self._nev
 
-    def max_events(self) -> int:
+    def _step_given(self, a: torch.Tensor, events: bool, npc_moves: torch.Tensor):
+        """step() with the NPCs' moves from the caller (orx_npc_step[_events])."""
+        self._require("orx_npc_step")
+        self._check_npc_moves(npc_moves)
+        if not events:
+            self._call("orx_npc_step", _ptr(a), _ptr(npc_moves), self.B, self.seed,
+                       self.game_offset, self._stream())
+            return self.status
+        if getattr(self, "_ev_given", None) is None:
+            self._ev_given = torch.zeros((self.B, self.max_events(given=True), 4),
+                                         dtype=torch.int32, device=self.device)
+            self._nev_given = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self._call("orx_npc_step_events", _ptr(a), _ptr(npc_moves), _ptr(self._ev_given),
+                   _ptr(self._nev_given), self.B, self.seed, self.game_offset, self._stream())
+        return self.status, self._ev_given, self._nev_given
+
+    def _check_npc_moves(self, t: torch.Tensor, n_ticks: Optional[int] = None) -> None:
+        # the kernels index [n_npcs, n_games] blindly, as they do the actions
+        if self.K == 0:
+            raise ValueError("npc_moves needs a configuration with NPCs (n_npcs > 0)")
+        shape = (self.K, self.B) if n_ticks is None else (n_ticks, self.K, self.B)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int8 or tuple(t.shape) != shape \
+                or not t.is_contiguous() or t.device != self.device:
+            what = "[n_npcs, n_games]" if n_ticks is None else "[T, n_npcs, n_games]"
+            raise ValueError(f"npc_moves must be a contiguous int8 {what} = {shape} tensor on "
+                             f"{self.device}")
+
+    def max_events(self, given: bool = False) -> int:
         """Event records per game-tick of ``step(events=True)`` for this
         configuration (orx_max_events: MAX_EVENTS, or 6 + 2 K with moving
-        NPCs)."""
-        n = int(self.lib.orx_max_events(self._pcfg))
-        _lib.check("orx_max_events", min(n, 0))
+        NPCs); ``given``: of ``step(events=True, npc_moves=...)``
+        (orx_npc_max_events: 6 + 2 K or MAX_EVENTS, whatever cfg.npc_policy)."""
+        name = "orx_npc_max_events" if given else "orx_max_events"
+        if given:
+            self._require(name)
+        n = int(getattr(self.lib, name)(self._pcfg))
+        _lib.check(name, min(n, 0))
         return n
 
+    def npc_state(self):
+        """``(x, y, health, alive)`` of every NPC slot, int32 tensors [n_npcs,
+        n_games] on the device (row k: iden 3 + k; alive 0 / 1),
+        decoded from npc_pos / npc_health / npc_alive with torch ops: what a
+        policy for the NPCs observes before it fills ``npc_moves``.  Slots
+        whose ``alive`` is 0 hold stale cells."""
+        K = self.K
+        pos = self.npc_pos[:K].to(torch.int32) & 0xFFFF
+        k = torch.arange(K, device=self.device)
+        words = self.npc_alive.reshape(-1, self.B)[k // 32].to(torch.int64) & 0xFFFFFFFF
+        alive = ((words >> (k % 32)[:, None]) & 1).to(torch.int32)
+        return pos & 0xFF, pos >> 8, self.npc_health[:K].to(torch.int32), alive
+
     def step_n(self, actions: torch.Tensor, obs: Optional[torch.Tensor] = None,
-               obs_format: int = OBS_INT32) -> torch.Tensor:
+               obs_format: int = OBS_INT32,
+               npc_moves: Optional[torch.Tensor] = None) -> torch.Tensor:
         """orx_step_n: ``actions`` int8 [T, n_games, 2] (a move log: tick t plays
         actions[t]) stepped in one launch, exactly as T calls of ``step`` would;
         ``obs`` (int32 [T, obs_rows(obs_format), n_games], optional) receives
-        every tick's observation.  Returns the status tensor."""
+        every tick's observation.  ``npc_moves`` (int8 [T, n_npcs, n_games]):
+        step t plays npc_moves[t] as ``step(npc_moves=...)`` would
+        (orx_npc_step_n).  Returns the status tensor."""
         if actions.dtype != torch.int8 or actions.dim() != 3 or actions.shape[1:] != (self.B, 2) \
                 or not actions.is_contiguous() or actions.device != self.device:
             raise ValueError(f"actions must be a contiguous int8 [T, n_games, 2] tensor on "
                              f"{self.device}")
         T = int(actions.shape[0])
         self._check_traj(T, obs, None, obs_format)
+        if npc_moves is not None:
+            self._require("orx_npc_step_n")
+            self._check_npc_moves(npc_moves, T)
+            self._call("orx_npc_step_n", _ptr(actions), _ptr(npc_moves), T, _ptr(obs),
+                       int(obs_format), self.B, self.seed, self.game_offset,
+                       int(self.concurrency), self._stream())
+            return self.status
         self._call("orx_step_n_ex", _ptr(actions), T, _ptr(obs), int(obs_format), self.B,
                    self.seed, self.game_offset, int(self.concurrency), self._stream())
         return self.status
@@ -412,13 +476,15 @@ class BatchedEngine:
     def env_step_slot(self, p2: int, obs: torch.Tensor, reward: torch.Tensor,
                       done: torch.Tensor, status: torch.Tensor,
                       bad_actions: Optional[torch.Tensor] = None):
-        """A callable ``launch(actions_ptr, nb, cols, outs=None)`` --
-        orx_env_step_args over one prebuilt argument block for this output set
-        (VecEnv.step's ring of preallocated outputs: per call the actions
+        """A callable ``launch(actions_ptr, nb, cols, outs=None, npc_ptr=None)``
+        -- orx_env_step_args over one prebuilt argument block for this output
+        set (VecEnv.step's ring of preallocated outputs: per call the actions
         pointer, the current stream and whatever changed since the last call
         are written into the block, and ctypes passes one pointer; ``outs``,
-        four data pointers, redirects the block to fresh outputs).  The caller
-        has checked the tensors."""
+        four data pointers, redirects the block to fresh outputs).  With
+        ``npc_ptr`` (the data pointer of an int8 [n_npcs, n_games] table) the
+        same block goes to orx_npc_env_step: the tick with those NPC moves.
+        The caller has checked the tensors."""
         a = _lib.OrxEnvStepArgs()
         a.cfg = ctypes.pointer(self._ccfg)
         a.st = ctypes.pointer(self._st)
@@ -429,11 +495,12 @@ class BatchedEngine:
         a.bad_actions = None if bad_actions is None else bad_actions.data_ptr()
         a.n_games = self.B
         fn, check, ref = self.lib.orx_env_step_args, _lib.check, ctypes.byref(a)
+        fn_npc = getattr(self.lib, "orx_npc_env_step", None)
         stream = _raw_stream_getter(self.device)
         eng = self
         last = [None, None, None, None]   # nb, cols, seed, game_offset in the block
 
-        def launch(a_ptr, nb, cols, outs=None):
+        def launch(a_ptr, nb, cols, outs=None, npc_ptr=None):
             if outs is not None:   # (fresh outputs: their four pointers this call)
                 a.obs, a.reward, a.done, a.status = outs
             a.actions = a_ptr
@@ -445,6 +512,13 @@ class BatchedEngine:
                 a.seed, a.game_offset = eng.seed, eng.game_offset
                 last[2], last[3] = eng.seed, eng.game_offset
             a.stream = stream()
+            if npc_ptr is not None:
+                if fn_npc is None:
+                    eng._require("orx_npc_env_step")
+                code = fn_npc(ref, npc_ptr)
+                if code:
+                    check("orx_npc_env_step", code)
+                return
             code = fn(ref)
             if code:
                 check("orx_env_step_args", code)

@@ -24,6 +24,11 @@ Construction mirrors the reference's plugins:
                  NpcPolicy.Stay (the reference's own hook), Random or Chase
                  (include/orx.h ORX_NPC_*); the engine then resolves the NPCs'
                  moves as the reference's update does (:116-145).
+
+The hook itself is there too: ``BatchedUpdater.update(..., npc_moves)`` takes
+every NPC's move as a table, and a ``GameUpdater`` subclass may override
+``decide_npc_move(game_state, ent, result)`` as it would the reference's
+(include/orx_npc.h has the rules: the built-in AIs' guards apply to the moves).
 """
 from __future__ import annotations
 
@@ -76,10 +81,14 @@ class BatchedUpdater:
     def n_games(self) -> int:
         return self.engine.B
 
-    def update(self, player1_moves, player2_moves) -> torch.Tensor:
+    def update(self, player1_moves, player2_moves, npc_moves=None) -> torch.Tensor:
         """One tick of every game (Updater.update).  Moves: Move values 1..5,
         one per game (sequence, numpy array or tensor).  Returns the int32
-        UpdateResult tensor (device; ORX status >= 16 for invalid moves)."""
+        UpdateResult tensor (device; ORX status >= 16 for invalid moves).
+        ``npc_moves`` ([n_npcs, n_games], row k: the NPC with iden 3 + k): what
+        an overridden Updater.decide_npc_move would return for each NPC; the
+        tick is then played with them instead of ``npc_policy``'s
+        (orx_npc_step)."""
         dev = self.engine.device
         m1 = torch.as_tensor(player1_moves, dtype=torch.int8).to(dev)
         m2 = torch.as_tensor(player2_moves, dtype=torch.int8).to(dev)
@@ -87,6 +96,13 @@ class BatchedUpdater:
             raise ValueError("one move per game and player")
         self.engine.actions[:, 0] = m1.reshape(-1)
         self.engine.actions[:, 1] = m2.reshape(-1)
+        if npc_moves is not None:
+            t = torch.as_tensor(npc_moves)
+            if tuple(t.shape) != (self.engine.K, self.n_games):
+                raise ValueError("npc_moves: one move per NPC slot and game ([n_npcs, n_games])")
+            # (out-of-range values become the invalid move 0 before the int8 cast)
+            t = torch.where((t >= 1) & (t <= 5), t, torch.zeros((), dtype=t.dtype))
+            return self.engine.step(npc_moves=t.to(torch.int8).to(dev).contiguous())
         return self.engine.step()
 
     def bot_moves(self, p1: Policy = Policy.Random, p2: Policy = Policy.Random) -> torch.Tensor:
@@ -126,15 +142,40 @@ class GameUpdater:
         self.engine.reset()
         return self.engine.game_states([0])[0]
 
+    def decide_npc_move(self, game_state, ent, result):  # pylint: disable=unused-argument
+        """The reference's hook (updater.py:165-178): the move NPC ``ent`` makes
+        this tick.  A subclass that overrides it drives the enemies: ``update``
+        then calls it once per NPC, in ``game_state.entities`` order, before
+        anything moves (updater.py:118-126; ``result`` is the tick's update
+        list so far, empty at that point as in the reference), and plays the
+        returned moves (orx_npc_step_events) behind the built-in AIs' guards
+        (include/orx_npc.h).  Not overridden, ``npc_policy`` decides."""
+        return Move.Stay
+
+    def _hook_moves(self, game_state):
+        """The overridden hook's moves as the engine's table int8 [n_npcs, 1],
+        or None when the hook is the base class's."""
+        if type(self).decide_npc_move is GameUpdater.decide_npc_move or self.engine.K == 0:
+            return None
+        players = (game_state.player_1_iden, game_state.player_2_iden)
+        table = torch.full((self.engine.K, 1), int(Move.Stay), dtype=torch.int8)
+        result = []
+        for ent in game_state.entities:
+            if ent.iden in players:
+                continue
+            table[ent.iden - 3, 0] = int(Move(int(self.decide_npc_move(game_state, ent, result))))
+        return table.to(self.engine.device)
+
     def update(self, game_state, player1_move, player2_move):
         from .compat import DungeonView
         from .updates import from_events
         eng = self.engine
         Move(int(player1_move)), Move(int(player2_move))  # ValueError like Move(...) would
         pre = {e.iden: e.depth for e in game_state.entities}
+        npc_moves = self._hook_moves(game_state)
         eng.actions[0, 0] = int(player1_move)
         eng.actions[0, 1] = int(player2_move)
-        status, ev, n = eng.step(events=True)
+        status, ev, n = eng.step(events=True, npc_moves=npc_moves)
         rows = [tuple(int(v) for v in r) for r in ev[0, : int(n[0])].cpu().numpy()]
         snap = eng.snapshot()
         cfg = eng.cfg

@@ -255,7 +255,26 @@ class VecEnv:
     def _max_move(self) -> int:
         return 6 if int(self.engine.cfg.flags) & EXT_HEAL else 5
 
-    def step(self, actions: torch.Tensor):
+    def _npc_table(self, npc_moves: torch.Tensor) -> torch.Tensor:
+        """``npc_moves`` as the int8 [n_npcs, n_games] table the launch reads:
+        an int8 tensor as it is; another integer dtype with every value
+        outside 1..5 mapped to the invalid move 0 before the int8 cast (257
+        must not wrap to 1), on the device, no host sync."""
+        K = self.engine.K
+        if K == 0:
+            raise ValueError("npc_moves needs a configuration with NPCs (n_npcs > 0)")
+        if not isinstance(npc_moves, torch.Tensor) or tuple(npc_moves.shape) != (K, self.B):
+            raise ValueError(f"npc_moves must be a [n_npcs, n_games] = ({K}, {self.B}) tensor, "
+                             f"got {tuple(getattr(npc_moves, 'shape', ()))}")
+        if BatchedEngine._ACTION_BYTES.get(npc_moves.dtype) is None:
+            raise ValueError(f"npc_moves must be an integer tensor, got {npc_moves.dtype}")
+        t = npc_moves if npc_moves.device == self.device else npc_moves.to(self.device)
+        if t.dtype != torch.int8:
+            t = torch.where((t >= 1) & (t <= 5), t,
+                            torch.zeros((), dtype=t.dtype, device=t.device)).to(torch.int8)
+        return t if t.is_contiguous() else t.contiguous()
+
+    def step(self, actions: torch.Tensor, npc_moves: Optional[torch.Tensor] = None):
         """Plays one tick: ``actions`` integer [n_games] (player 1; the opponent
         policy moves player 2) or [n_games, 2] (self-play), Move values 1..5
         (1..6 with EXT_HEAL), any integer dtype.  A value outside them (e.g. a
@@ -265,7 +284,14 @@ class VecEnv:
         warning by default; class docstring).  One launch (orx_env_step_ex) and no host sync
         (unless check_actions=True).  Returns (observation int32 [n_games,
         14], reward float32, done bool, status int32 [n_games]): separate
-        tensors, fresh ones unless ``out_buffers`` > 0."""
+        tensors, fresh ones unless ``out_buffers`` > 0.
+
+        ``npc_moves`` (integer [n_npcs, n_games], row k: NPC iden 3 + k, Move
+        values 1..5) plays the tick with these NPC moves instead of
+        cfg.npc_policy's (orx_npc_env_step, include/orx_npc.h; what a policy
+        for the NPCs sees is ``engine.npc_state()``): still one launch and no
+        host sync.  A value outside 1..5 for a live NPC stops that game like a
+        bad action, and counts with them."""
         shape = actions.shape
         if shape != self._shape1 and shape != self._shape2:   # no silent broadcasting
             raise ValueError(f"actions must be [n_games] or [n_games, 2], got {tuple(shape)}")
@@ -284,8 +310,10 @@ class VecEnv:
                                  "0-based: add 1)")
         if self._stock is None:   # (decided at the first step)
             self._stock = getattr(self.engine, "mt_py", None) is not None
+        npc = None if npc_moves is None else self._npc_table(npc_moves)
         if self._stock:   # stock-seed mode
-            return self._step_stock(a)
+            return self._step_stock(a, npc)
+        npc_ptr = None if npc is None else npc.data_ptr()
         deferred = self._bad_host is not None
         bad = self._bad_ptr if deferred else None
         if deferred:   # (before the launch: a call that raises plays no tick)
@@ -300,19 +328,24 @@ class VecEnv:
             if go is None:   # one prebuilt argument block per output set
                 go = self._ring_launch[k] = self.engine.env_step_slot(
                     self._p2, *out, self._bad_dev if deferred else None)
-            go(a.data_ptr(), nb, len(shape))
+            if npc_ptr is None:
+                go(a.data_ptr(), nb, len(shape))
+            else:
+                go(a.data_ptr(), nb, len(shape), None, npc_ptr)
         else:
             out = self._alloc_out()
             obs, reward, done, status = out
             if self._fresh_launch is None:   # one argument block, its outputs set per call
                 self._fresh_launch = self.engine.env_step_slot(
                     self._p2, *out, self._bad_dev if deferred else None)
-            self._fresh_launch(a.data_ptr(), nb, len(shape),
-                               (obs.data_ptr(), reward.data_ptr(), done.data_ptr(),
-                                status.data_ptr()))
+            outs = (obs.data_ptr(), reward.data_ptr(), done.data_ptr(), status.data_ptr())
+            if npc_ptr is None:
+                self._fresh_launch(a.data_ptr(), nb, len(shape), outs)
+            else:
+                self._fresh_launch(a.data_ptr(), nb, len(shape), outs, npc_ptr)
         return out
 
-    def _step_stock(self, a: torch.Tensor):
+    def _step_stock(self, a: torch.Tensor, npc: Optional[torch.Tensor] = None):
         """Stock-seed mode (the bots draw from each game's own MT19937 stream):
         orx_policy + orx_step, invalid values mapped on the device to the
         invalid move 0 before the int8 cast (257 must not wrap to 1)."""
@@ -326,7 +359,7 @@ class VecEnv:
         else:
             e.actions.copy_(a)
         before = e.status.clone()
-        status = e.step(e.actions).clone()
+        status = e.step(e.actions, npc_moves=npc).clone()
         reward, done = self.outcome(before, status)
         if self._bad_host is not None:   # the deferred check, counted with torch ops here
             self._bad_dev += ((before == UpdateResult.InProgress)
