@@ -87,7 +87,8 @@ _OPTIONAL = {
     "orx_step_n_ex": (_int, [_cfg, _st, vp, i32, vp, i32, i64, u64, i64, i32, vp]),
     "orx_env_step_args": (_int, [ctypes.POINTER(OrxEnvStepArgs)]),
 }
-# include/orx_view.h, orx_path.h, orx_moves.h, orx_npc.h (EXPORTS is orx.h alone); optional too
+# include/orx_view.h, orx_path.h, orx_moves.h, orx_npc.h, orx_npc_query.h (EXPORTS is orx.h
+# alone); optional too
 _VIEW = {"orx_view": (_int, [_cfg, _st, i32, i32, vp, vp, i64, vp])}
 _PATH = {
     "orx_path_field": (_int, [_cfg, vp, vp, vp]),
@@ -108,12 +109,19 @@ _NPC = {
     "orx_npc_env_step": (_int, [ctypes.POINTER(OrxEnvStepArgs), vp]),
     "orx_npc_build_id": (_str, []),
 }
+# include/orx_npc_query.h
+_NPC_QUERY = {
+    "orx_npc_options": (_int, [_cfg, _st, vp, vp, vp, vp, i64, vp]),
+    "orx_npc_seek": (_int, [_cfg, _st, vp, vp, vp, vp, i64, vp]),
+    "orx_npc_query_build_id": (_str, []),
+}
 
 EXPORTS = tuple(_REQUIRED) + tuple(_OPTIONAL)
 VIEW_EXPORTS = tuple(_VIEW)
 PATH_EXPORTS = tuple(_PATH)
 MOVES_EXPORTS = tuple(_MOVES)
 NPC_EXPORTS = tuple(_NPC)
+NPC_QUERY_EXPORTS = tuple(_NPC_QUERY)
 
 
 def load() -> ctypes.CDLL:
@@ -127,7 +135,7 @@ def load() -> ctypes.CDLL:
         raise RuntimeError(f"HIP engine library missing: {LIB_PATH} -- run "
                            "`python -m optimax_rogue_amd.build` first")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC):
+    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC, _NPC_QUERY):
         for name, (restype, argtypes) in table.items():
             if table is _REQUIRED or hasattr(L, name):   # (a missing required symbol raises)
                 fn = getattr(L, name)
@@ -169,3 +177,10 @@ def npc_build_id() -> str:
     "" for a library built before include/orx_npc.h)."""
     L = load()
     return L.orx_npc_build_id().decode() if hasattr(L, "orx_npc_build_id") else ""
+
+
+def npc_query_build_id() -> str:
+    """orx_npc_query_build_id() of the loaded library (build.npc_query_id() of
+    its sources; "" for a library built before include/orx_npc_query.h)."""
+    L = load()
+    return L.orx_npc_query_build_id().decode() if hasattr(L, "orx_npc_query_build_id") else ""

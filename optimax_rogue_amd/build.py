@@ -43,6 +43,9 @@ PLAN_HDR = os.path.join(PKG_DIR, "csrc", "orx_plan.h")   # the engine's launch p
 # the tick with the NPCs' moves from the caller (orx_npc_*): defined in the
 # engine's source (it needs the moving-NPC tick), declared in a header of its own
 NPC_HDR = os.path.join(ROOT, "include", "orx_npc.h")
+# the enemies' queries (orx_npc_options / orx_npc_seek): one more object
+NPC_QUERY_SRC = os.path.join(PKG_DIR, "csrc", "orx_npc_query.hip")
+NPC_QUERY_HDR = os.path.join(ROOT, "include", "orx_npc_query.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -73,8 +76,15 @@ PARTS = {
     "moves": Part("orx_moves_build_id", "ORX_MOVES_BUILD_ID", (MOVES_SRC, MOVES_HDR, QUERY_HDR),
                   (MOVES_SRC,)),
     "npc": Part("orx_npc_build_id", "ORX_NPC_BUILD_ID", (NPC_HDR, SRC), ()),
+    # (no `sources`: like "npc" it is read only with built_ids(every=True), so the
+    # parts a caller sees without it stay engine, path and moves; its object is
+    # named in EXTRA_SOURCES)
+    "npc_query": Part("orx_npc_query_build_id", "ORX_NPC_QUERY_BUILD_ID",
+                      (NPC_QUERY_SRC, NPC_QUERY_HDR, QUERY_HDR), ()),
 }
-SOURCES = [src for p in PARTS.values() for src in p.sources]   # (SRC first: _build_parts splits it)
+EXTRA_SOURCES = [NPC_QUERY_SRC]
+# (SRC first: _build_parts splits it)
+SOURCES = [src for p in PARTS.values() for src in p.sources] + EXTRA_SOURCES
 
 
 def hipcc() -> str:
@@ -115,12 +125,18 @@ def npc_id() -> str:
     return tree_ids()["npc"]
 
 
+def npc_query_id() -> str:
+    """What orx_npc_query_build_id() of a library built from these sources returns."""
+    return tree_ids()["npc_query"]
+
+
 def built_ids(path: str = OUT, every: bool = False):
     """``tree_ids``'s dict for the library at `path` ("" for a part it was built
     without; None if it cannot be loaded), read in one child process so this
     one does not map a library that a later build replaces.  The parts
     compiled from sources of their own; with ``every`` also those defined in
-    another part's source ("npc", whose id follows its header too)."""
+    another part's source ("npc", whose id follows its header too) or in
+    EXTRA_SOURCES ("npc_query")."""
     parts = {name: p for name, p in PARTS.items() if every or p.sources}
     code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1])\n"
             "for f in (getattr(L,s,None) for s in sys.argv[2:]):\n"
@@ -179,8 +195,9 @@ def _build_locked(out: str, ids: dict, defines, verbose: bool) -> str:
 # the host side, every kernel instance declared extern; parts 1..NPARTS-1:
 # their share of the explicit instantiations, orx_engine.hip "Kernel
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
-# translation unit.  The other SOURCES (orx_view.hip, orx_path.hip and
-# orx_moves.hip: small) are one more object each, compiled last.
+# translation unit.  The other SOURCES (orx_view.hip, orx_path.hip,
+# orx_moves.hip and orx_npc_query.hip: small) are one more object each,
+# compiled last.
 NPARTS = 17
 
 

@@ -720,6 +720,104 @@ class BatchedEngine:
         self._call("orx_moves", int(player), _ptr(kind), None, None, self.B, self._stream())
         return kind
 
+    # -- the enemies' queries (include/orx_npc_query.h) ------------------------
+    def _require_npc_query(self, name: str) -> None:
+        if self.K == 0:
+            raise ValueError("the NPC queries need a configuration with NPCs (n_npcs > 0)")
+        self._require(name)
+
+    def npc_options(self, out=None):
+        """orx_npc_options (include/orx_npc_query.h): what each move of every
+        NPC would do in every game, as ``(kind, target, amount, where)``: uint8,
+        int16 and int16 [n_npcs, n_games, MOVES_COLS = 8], slot-major like
+        ``npc_moves`` (row k: iden 3 + k), column ``m`` for Move ``m``, and
+        uint8 [n_games], the state of the NPCs' depth (NPC_DEPTH_WATCHED,
+        UNWATCHED, GONE).  ``kind`` is the outcome NPC_OUT_* (REST, FROZEN,
+        BLOCKED, STEP, STAIRS, ATTACK_NPC, ATTACK_PLAYER, NONE) with the
+        NPC_OUT_LETHAL flag, ``target`` the iden an attack hits (-1
+        otherwise), ``amount`` its damage.  FROZEN and BLOCKED are the moves
+        the engine's guards (include/orx_npc.h) replace with Stay.  One launch
+        on the current stream from the resident state, no host sync, no state
+        change, no random words; it can be captured in a graph beside a step.
+        ``out``: a ``(kind, target, amount, where)`` tuple of tensors written
+        and returned instead of fresh ones.  The host reference is
+        ``npc_query.options(self.snapshot(), cfg)``."""
+        from .moves import MOVES_COLS
+        self._require_npc_query("orx_npc_options")
+        shape = (self.K, self.B, MOVES_COLS)
+        outs = self._outs(out, [(torch.uint8, shape), (torch.int16, shape), (torch.int16, shape),
+                                (torch.uint8, (self.B,))], "(kind, target, amount, where)",
+                          align=16, distinct=("kind", "target", "amount", "where"))
+        self._call("orx_npc_options", _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]),
+                   self.B, self._stream())
+        return tuple(outs)
+
+    def npc_options_kind(self):
+        """``(kind, where)`` of ``npc_options()`` alone: orx_npc_options with
+        target and amount NULL (what a mask needs; a fifth of the stores)."""
+        from .moves import MOVES_COLS
+        self._require_npc_query("orx_npc_options")
+        kind = torch.empty((self.K, self.B, MOVES_COLS), dtype=torch.uint8, device=self.device)
+        where = torch.empty(self.B, dtype=torch.uint8, device=self.device)
+        self._call("orx_npc_options", _ptr(kind), None, None, _ptr(where), self.B, self._stream())
+        return kind, where
+
+    def npc_action_mask(self) -> torch.Tensor:
+        """bool [n_npcs, n_games, 5]: column ``j`` is Move ``j + 1``, True where
+        the engine would play that byte of ``npc_moves`` as given (not
+        NPC_OUT_FROZEN, not NPC_OUT_BLOCKED).  Stay is always True; a dead slot
+        has only Stay True, so a masked softmax is never empty; the live slots
+        of an UNWATCHED game are all True (``npc_query.action_mask``).  Torch
+        ops on the device behind one launch, no sync."""
+        from .npc_query import action_mask
+        return action_mask(*self.npc_options_kind())
+
+    def npc_seek(self, out=None):
+        """orx_npc_seek (include/orx_npc_query.h): how many moves every NPC of
+        every game is from player 1, player 2 and the nearer of the two along
+        walkable cells of the NPCs' depth, and the move that gets it one step
+        closer.  Returns ``(dist, move, target)``: int32, int8 and int16
+        [n_npcs, n_games, SEEK_COLS = 4], columns NPC_SEEK_P1, NPC_SEEK_P2,
+        NPC_SEEK_NEAREST and one of padding; ``dist`` is SEEK_UNREACHABLE (-1)
+        or SEEK_ABSENT (-2) as in ``seek``, ``target`` the player's iden (-1:
+        none).  A walk may not cross a staircase; entities and the freeze guard
+        are ignored (``npc_options`` tells what the move would do).  One launch,
+        no host sync, no state change; with a bank the first call also builds
+        ``pair_field``.  ``out``: a ``(dist, move, target)`` tuple of tensors
+        written and returned instead of fresh ones.  The host reference is
+        ``npc_query.seek(self.snapshot(), cfg)``."""
+        from .path import SEEK_COLS
+        self._require_npc_query("orx_npc_seek")
+        shape = (self.K, self.B, SEEK_COLS)
+        outs = self._outs(out, [(torch.int32, shape), (torch.int8, shape), (torch.int16, shape)],
+                          "(dist, move, target)", align=16, distinct=("dist", "move", "target"))
+        pairs = self.pair_field
+        self._call("orx_npc_seek", _ptr(pairs), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                   self.B, self._stream())
+        return tuple(outs)
+
+    def npc_hunt_moves(self) -> torch.Tensor:
+        """int8 [n_npcs, n_games], ready to pass as ``npc_moves``: every NPC's
+        first move toward the nearer player (``npc_seek``'s column
+        NPC_SEEK_NEAREST) where ``npc_options`` calls that move STEP or
+        ATTACK_PLAYER, and Stay otherwise -- a pursuit that walks round walls,
+        never steps onto a staircase and never hits a fellow NPC
+        (``npc_query.hunt_moves``).  Two launches and torch ops on the device,
+        no sync; with a bank, call it (or ``npc_seek``) once before capturing
+        a graph."""
+        from .enums import (Move, NPC_OUT_ATTACK_PLAYER, NPC_OUT_MASK, NPC_OUT_STEP,
+                            NPC_SEEK_NEAREST)
+        from .path import SEEK_COLS
+        self._require_npc_query("orx_npc_seek")
+        kind, _ = self.npc_options_kind()
+        move = torch.empty((self.K, self.B, SEEK_COLS), dtype=torch.int8, device=self.device)
+        self._call("orx_npc_seek", _ptr(self.pair_field), None, _ptr(move), None, self.B,
+                   self._stream())
+        m = move[:, :, NPC_SEEK_NEAREST]
+        k = torch.gather(kind, 2, m.to(torch.int64).unsqueeze(2)).squeeze(2) & NPC_OUT_MASK
+        ok = (k == NPC_OUT_STEP) | (k == NPC_OUT_ATTACK_PLAYER)
+        return torch.where(ok, m, int(Move.Stay))
+
     def _check_actions(self, a: torch.Tensor, what: str) -> None:
         # the kernels index [n_games, 2] blindly: a wrong buffer would be an
         # out-of-bounds device access, so it is refused here

@@ -124,3 +124,21 @@ SEP_PERIOD_MAX = 1 << 24   # ORX_SEP_PERIOD_MAX: cfg.sep_period's upper bound
 # update-event records of orx_step_events (include/orx.h ORX_EV_*)
 EV_COMBAT, EV_DEATH, EV_POSITION, EV_DUNGEON, EV_HEALTH = 1, 2, 3, 4, 5
 MAX_EVENTS = 8
+
+# the enemies' queries (include/orx_npc_query.h): the state of the NPCs' depth
+# (ORX_NPC_DEPTH_*), what a move of an NPC would do (ORX_NPC_OUT_*: bits 0-2,
+# NPC_OUT_LETHAL above) and the columns of orx_npc_seek's rows (ORX_NPC_SEEK_*)
+NPC_DEPTH_GONE, NPC_DEPTH_WATCHED, NPC_DEPTH_UNWATCHED = 0, 1, 2
+NPC_OUT_MASK = 7
+NPC_OUT_NONE = 0
+NPC_OUT_REST = 1
+NPC_OUT_BLOCKED = 2
+NPC_OUT_STEP = 3
+NPC_OUT_STAIRS = 4
+NPC_OUT_ATTACK_NPC = 5
+NPC_OUT_ATTACK_PLAYER = 6
+NPC_OUT_FROZEN = 7
+NPC_OUT_LETHAL = 8
+NPC_OUT_NAMES = ("NONE", "REST", "BLOCKED", "STEP", "STAIRS", "ATTACK_NPC", "ATTACK_PLAYER",
+                 "FROZEN")
+NPC_SEEK_P1, NPC_SEEK_P2, NPC_SEEK_NEAREST = 0, 1, 2

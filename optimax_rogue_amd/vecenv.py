@@ -187,6 +187,36 @@ class VecEnv:
         dist, move, _ = self.engine.seek(player=player)
         return torch.where(dist[:, 0] > 0, move[:, 0], self.stair_moves(player))
 
+    # the enemies' side (include/orx_npc_query.h): what a policy for the NPCs
+    # needs before it fills ``step``'s ``npc_moves``
+    def npc_options(self, out=None):
+        """``(kind, target, amount, where)``: what each move of every NPC of
+        every game would do, [n_npcs, n_games, 8] each (row k: NPC iden 3 + k,
+        column ``m``: Move ``m``), and the state of the NPCs' depth [n_games]
+        (``BatchedEngine.npc_options``; one launch, no host sync)."""
+        return self.engine.npc_options(out=out)
+
+    def npc_action_mask(self) -> torch.Tensor:
+        """bool [n_npcs, n_games, 5]: column ``j`` is Move ``j + 1``, False
+        where the engine's guards would play a Stay in the byte's place; Stay
+        is always allowed (``BatchedEngine.npc_action_mask``)."""
+        return self.engine.npc_action_mask()
+
+    def npc_seek(self, out=None):
+        """``(dist, move, target)`` of every NPC of every game, [n_npcs,
+        n_games, 4] each: how many moves away player 1, player 2 and the nearer
+        of the two are along walkable cells, and the move that gets one step
+        closer (``BatchedEngine.npc_seek``; one launch, no host sync)."""
+        return self.engine.npc_seek(out=out)
+
+    def npc_hunt_moves(self) -> torch.Tensor:
+        """int8 [n_npcs, n_games]: every NPC's step along a shortest walk to
+        the nearer player, or its attack next to it; Stay where that move
+        would be a staircase, a fellow NPC or nothing at all -- a scripted
+        pursuit ready as ``step``'s ``npc_moves``
+        (``BatchedEngine.npc_hunt_moves``)."""
+        return self.engine.npc_hunt_moves()
+
     @staticmethod
     def outcome(before: torch.Tensor, after: torch.Tensor):
         """(reward, done) of a transition between two status tensors.  A game
