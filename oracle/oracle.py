@@ -59,6 +59,8 @@ def lib():
         vp, i64, i32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
         L.oracle_new.restype = vp
         L.oracle_new.argtypes = [ctypes.POINTER(_Cfg), i64, u64, i64, ctypes.c_int]
+        L.oracle_clone.restype = vp
+        L.oracle_clone.argtypes = [vp]
         L.oracle_free.argtypes = [vp]
         L.oracle_reset.argtypes = [vp, vp, vp]
         L.oracle_step.argtypes = [vp, vp]
@@ -123,6 +125,15 @@ class Oracle:
             except Exception:  # interpreter shutdown: the module's globals are gone
                 pass
             self._h = None
+
+    def clone(self) -> "Oracle":
+        """A deep copy in the same state (games, generators, bank): several
+        continuations of one rolled state without rolling it again."""
+        twin = object.__new__(Oracle)
+        twin.cfg, twin.B, twin.K, twin._c, twin.layouts = (self.cfg, self.B, self.K, self._c,
+                                                           self.layouts)
+        twin._h = lib().oracle_clone(self._h)
+        return twin
 
     def reset(self, mask=None, episode=None):
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)

@@ -1,7 +1,7 @@
 /* TEST INFRASTRUCTURE ONLY: drives the C oracle (orx_oracle.c) through every
  * mode it has -- NPCs (dense and at the K cap), both despawn strategies,
  * Separated starts, a dungeon bank, the build extensions, stock-seed (MT19937)
- * mode, event recording, invalid actions -- so that a build with
+ * mode, event recording, invalid actions, deep copies -- so that a build with
  * -fsanitize=address,undefined (tests/test_sanitize.py) checks the oracle
  * itself for memory errors and undefined behaviour. */
 #include <stdint.h>
@@ -14,6 +14,7 @@
 void* oracle_new(const orx_cfg_t* cfg, int64_t n_games, uint64_t seed, int64_t game_offset,
                  int record_events);
 void oracle_set_bank(void* h, const uint8_t* tiles, int32_t n_layouts);
+void* oracle_clone(const void* h);
 void oracle_free(void* h);
 void oracle_reset(void* h, const uint8_t* mask, const int32_t* episode);
 void oracle_step(void* h, const int8_t* actions);
@@ -43,6 +44,16 @@ static void run(const char* name, orx_cfg_t c, int64_t B, int pol1, int pol2, in
   for (int t = 0; t < ticks; ++t) {
     oracle_policy(o, pol1, pol2, a);
     if (t == ticks / 2) a[0] = 9;  /* an invalid action stops that game */
+    if (t == ticks / 2) {
+      /* oracle_clone: a copy played and freed beside the original, then the
+       * original freed and the run continued in another copy */
+      void* side = oracle_clone(o);
+      void* next = oracle_clone(o);
+      oracle_step(side, a);
+      oracle_free(side);
+      oracle_free(o);
+      o = next;
+    }
     oracle_step(o, a);
     for (int64_t g = 0; g < B; g += 7) {
       oracle_events(o, g, buf, 1024);

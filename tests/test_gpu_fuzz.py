@@ -17,6 +17,10 @@ Bit-exact (all state is integer).  Reference-pinned where the configuration
 stays inside the reference's semantics (flags 0); engine-vs-oracle only
 ("parity unpinned") where a build extension is on.  The generator is seeded,
 so a failure names a reproducible case id.
+
+``_draw`` is shared: tests/query_sweep.py takes the same draws (at a base of
+its own) for the sweep of the six query kernels, so a change to the order or
+the number of its draws moves that sweep's cases too.
 """
 import os
 
