@@ -64,6 +64,8 @@ def lib():
         L.oracle_free.argtypes = [vp]
         L.oracle_reset.argtypes = [vp, vp, vp]
         L.oracle_step.argtypes = [vp, vp]
+        L.oracle_step_given.argtypes = [vp, vp, vp]
+        L.oracle_given_tally.argtypes = [vp, vp]
         L.oracle_policy.argtypes = [vp, i32, i32, vp]
         L.oracle_export.argtypes = [vp] + [vp] * 15
         for fn in ("oracle_world", "oracle_events", "oracle_entities"):
@@ -140,9 +142,34 @@ class Oracle:
         e = None if episode is None else np.ascontiguousarray(episode, np.int32)
         lib().oracle_reset(self._h, None if m is None else _ptr(m), None if e is None else _ptr(e))
 
-    def step(self, actions):
+    def step(self, actions, npc_moves=None):
+        """One tick.  ``npc_moves`` (int8 [n_npcs, n_games], slot-major) plays
+        it with the NPCs' moves from that table (include/orx_npc.h: the guards
+        around the byte, a bad byte of a live NPC stops the game, nothing
+        drawn for the NPCs) instead of cfg.npc_policy's."""
         a = np.ascontiguousarray(actions, np.int8).reshape(self.B, 2)
-        lib().oracle_step(self._h, _ptr(a))
+        if npc_moves is None:
+            lib().oracle_step(self._h, _ptr(a))
+            return
+        if self.K == 0 or self.cfg["flags"] & ~3:
+            raise ValueError("the given tick needs n_npcs > 0 and flags within 1 | 2")
+        t = np.asarray(npc_moves)
+        if t.dtype != np.int8 or t.shape != (self.K, self.B):
+            raise ValueError(f"npc_moves must be int8 [n_npcs, n_games] = ({self.K}, {self.B})")
+        t = np.ascontiguousarray(t)
+        lib().oracle_step_given(self._h, _ptr(a), _ptr(t))
+
+    GIVEN_TALLIES = ("guard1", "guard2", "guard3", "refused", "dead_bad", "npc_kill")
+
+    def given_tally(self) -> dict:
+        """Per game, int32 [n_games] each, over this oracle's life: how often
+        guard 1 / 2 / 3 replaced a non-Stay byte; game-ticks a bad byte of a
+        live slot refused; game-ticks played although a dead slot held a bad
+        byte; ticks (of either kind of step) that left a player at health <= 0
+        after an NPC's blow took health from it."""
+        out = np.zeros((len(self.GIVEN_TALLIES), self.B), np.int32)
+        lib().oracle_given_tally(self._h, _ptr(out))
+        return dict(zip(self.GIVEN_TALLIES, out))
 
     def policy(self, pol1: int, pol2: int, actions=None):
         a = (np.full((self.B, 2), 5, np.int8) if actions is None

@@ -1,7 +1,8 @@
 /* TEST INFRASTRUCTURE ONLY: drives the C oracle (orx_oracle.c) through every
  * mode it has -- NPCs (dense and at the K cap), both despawn strategies,
  * Separated starts, a dungeon bank, the build extensions, stock-seed (MT19937)
- * mode, event recording, invalid actions, deep copies -- so that a build with
+ * mode, event recording, invalid actions, deep copies, the tick with the NPCs'
+ * moves given (include/orx_npc.h) -- so that a build with
  * -fsanitize=address,undefined (tests/test_sanitize.py) checks the oracle
  * itself for memory errors and undefined behaviour. */
 #include <stdint.h>
@@ -23,6 +24,69 @@ void oracle_seed_mt(void* h, uint64_t seed);
 int32_t oracle_events(void* h, int64_t game, int32_t* out, int32_t cap);
 int32_t oracle_entities(void* h, int64_t game, int32_t* out, int32_t cap);
 int32_t oracle_world(void* h, int64_t game, int32_t* out, int32_t cap);
+
+void oracle_step_given(void* h, const int8_t* actions, const int8_t* npc_moves);
+void oracle_given_tally(void* h, int32_t* out);
+
+static orx_cfg_t base(int w, int h);
+
+/* The given tick (include/orx_npc.h) in stock-seed mode: a table of 1..5 from
+ * a small generator; every tick game 3 gets a byte outside the Move codes in
+ * a dead slot (nothing may stop), from the middle of the run on game 0 gets
+ * one in a live slot every 16th tick (the game stops), and at the middle the
+ * run continues in a clone. */
+static int run_given(const char* name) {
+  enum { B = 32, K = 6, TICKS = 240 };
+  orx_cfg_t c = base(8, 8);
+  c.n_npcs = K; c.rng = ORX_RNG_MT19937; c.max_ticks = 40;
+  void* o = oracle_new(&c, B, 7, 3, 1);
+  oracle_seed_mt(o, 11);
+  oracle_reset(o, NULL, NULL);
+  int8_t a[2 * B], table[K * B];
+  int32_t buf[4096];
+  uint32_t x = 12345u;
+  int bad_dead = 0, bad_live = 0;
+  for (int t = 0; t < TICKS; ++t) {
+    oracle_policy(o, 2, 1, a);
+    for (int i = 0; i < K * B; ++i) {
+      x = x * 1664525u + 1013904223u;
+      table[i] = (int8_t)(1 + (x >> 16) % 5u);
+    }
+    for (int g = 0; g < 4; g += 3) {   /* game 3: a dead slot; game 0 at half time: a live one */
+      int live[K] = {0};
+      int n = oracle_entities(o, g, buf, 512);
+      for (int j = 0; j < n; ++j)
+        if (buf[7 * j] >= 3) live[buf[7 * j] - 3] = 1;
+      for (int k = 0; k < K; ++k) {
+        if (g == 3 && !live[k]) { table[k * B + g] = -128; bad_dead = 1; break; }
+        if (g == 0 && t >= TICKS / 2 && t % 16 == 0 && live[k]) {
+          table[k * B + g] = 6; bad_live = 1; break;
+        }
+      }
+    }
+    if (t == TICKS / 2) {
+      void* next = oracle_clone(o);
+      oracle_step_given(o, a, table);
+      oracle_free(o);
+      o = next;
+    }
+    oracle_step_given(o, a, table);
+    for (int64_t g = 0; g < B; g += 7) {
+      oracle_events(o, g, buf, 1024);
+      oracle_entities(o, g, buf, 512);
+      oracle_world(o, g, buf, 1024);
+    }
+  }
+  int32_t tally[6 * B];
+  oracle_given_tally(o, tally);
+  /* rows: guards 1-3, refused, dead_bad, npc_kill */
+  const int ok = bad_dead && bad_live && tally[3 * B + 0] >= 1 && tally[3 * B + 3] == 0 &&
+                 tally[4 * B + 3] > 0;
+  oracle_free(o);
+  if (ok) printf("%s ok\n", name);
+  else printf("%s FAILED: the bad bytes did not land as planned\n", name);
+  return !ok;
+}
 
 static orx_cfg_t base(int w, int h) {
   orx_cfg_t c;
@@ -107,5 +171,5 @@ int main(void) {
   c = base(W, H);
   c.n_npcs = 2; c.despawn = ORX_DESPAWN_UNUSED;
   run("bank", c, 32, 2, 1, 300, tiles, L);
-  return 0;
+  return run_given("given");
 }

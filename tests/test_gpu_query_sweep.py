@@ -26,43 +26,12 @@ import pytest
 
 import moves_cases as mc
 import query_sweep as qs
+from guarded import POISONS, Guarded, same
 
 pytestmark = pytest.mark.gpu
 
 CASES = [qs.draw(c) for c in range(qs.N_CASES)]
-POISONS = (0xA5, 0x5A)
-LEAD = 64                  # guard bytes before and after an output
 TALLIES = {}               # case -> query_sweep.tally of the engine's state
-
-
-class Guarded:
-    """An output tensor of ``dtype`` and ``shape`` inside a byte buffer filled
-    with ``poison``, LEAD + ``skew`` bytes in (``skew`` 0: 16-byte aligned)."""
-
-    def __init__(self, dev, dtype, shape, poison, skew=0):
-        import torch
-        size = torch.empty((), dtype=dtype).element_size()
-        self.lead, self.n, self.poison = LEAD + skew, int(np.prod(shape)) * size, poison
-        self.buf = torch.full((self.lead + self.n + LEAD,), poison, dtype=torch.uint8, device=dev)
-        assert self.buf.data_ptr() % 16 == 0 and self.lead % size == 0
-        self.out = self.buf[self.lead:self.lead + self.n].view(dtype).view(shape)
-        assert self.out.data_ptr() % 16 == skew % 16
-
-    def check(self, want, what):
-        """The guards are intact and the output is ``want`` (numpy), exactly."""
-        buf = self.buf.cpu().numpy()
-        assert (buf[:self.lead] == self.poison).all(), (what, "bytes before the output written")
-        assert (buf[self.lead + self.n:] == self.poison).all(), (what, "bytes after it written")
-        same(self.out, want, what)
-
-
-def same(got, want, what):
-    got = got.cpu().numpy()
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        raise AssertionError(f"{what}: {len(bad)} cells differ, first at {bad[:5].tolist()}: got "
-                             f"{got[tuple(bad[0])]}, reference {want[tuple(bad[0])]}")
 
 
 def engine_state(d):

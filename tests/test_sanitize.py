@@ -24,4 +24,4 @@ def test_oracle_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     assert "runtime error" not in r.stderr
-    assert r.stdout.count(" ok") == 8, r.stdout
+    assert r.stdout.count(" ok") == 9, r.stdout
