@@ -115,6 +115,11 @@ _NPC_QUERY = {
     "orx_npc_seek": (_int, [_cfg, _st, vp, vp, vp, vp, i64, vp]),
     "orx_npc_query_build_id": (_str, []),
 }
+# include/orx_sight.h
+_SIGHT = {
+    "orx_sight": (_int, [_cfg, _st, i32, i32, vp, vp, vp, i64, vp]),
+    "orx_sight_build_id": (_str, []),
+}
 
 EXPORTS = tuple(_REQUIRED) + tuple(_OPTIONAL)
 VIEW_EXPORTS = tuple(_VIEW)
@@ -122,6 +127,7 @@ PATH_EXPORTS = tuple(_PATH)
 MOVES_EXPORTS = tuple(_MOVES)
 NPC_EXPORTS = tuple(_NPC)
 NPC_QUERY_EXPORTS = tuple(_NPC_QUERY)
+SIGHT_EXPORTS = tuple(_SIGHT)
 
 
 def load() -> ctypes.CDLL:
@@ -135,7 +141,7 @@ def load() -> ctypes.CDLL:
         raise RuntimeError(f"HIP engine library missing: {LIB_PATH} -- run "
                            "`python -m optimax_rogue_amd.build` first")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC, _NPC_QUERY):
+    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC, _NPC_QUERY, _SIGHT):
         for name, (restype, argtypes) in table.items():
             if table is _REQUIRED or hasattr(L, name):   # (a missing required symbol raises)
                 fn = getattr(L, name)
@@ -184,3 +190,10 @@ def npc_query_build_id() -> str:
     its sources; "" for a library built before include/orx_npc_query.h)."""
     L = load()
     return L.orx_npc_query_build_id().decode() if hasattr(L, "orx_npc_query_build_id") else ""
+
+
+def sight_build_id() -> str:
+    """orx_sight_build_id() of the loaded library (build.sight_id() of its
+    sources; "" for a library built before include/orx_sight.h)."""
+    L = load()
+    return L.orx_sight_build_id().decode() if hasattr(L, "orx_sight_build_id") else ""

@@ -46,6 +46,9 @@ NPC_HDR = os.path.join(ROOT, "include", "orx_npc.h")
 # the enemies' queries (orx_npc_options / orx_npc_seek): one more object
 NPC_QUERY_SRC = os.path.join(PKG_DIR, "csrc", "orx_npc_query.hip")
 NPC_QUERY_HDR = os.path.join(ROOT, "include", "orx_npc_query.h")
+# line of sight through the walls of orx_view's window (orx_sight): one more object
+SIGHT_SRC = os.path.join(PKG_DIR, "csrc", "orx_sight.hip")
+SIGHT_HDR = os.path.join(ROOT, "include", "orx_sight.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -81,8 +84,11 @@ PARTS = {
     # named in EXTRA_SOURCES)
     "npc_query": Part("orx_npc_query_build_id", "ORX_NPC_QUERY_BUILD_ID",
                       (NPC_QUERY_SRC, NPC_QUERY_HDR, QUERY_HDR), ()),
+    # (the same: its object is named in EXTRA_SOURCES)
+    "sight": Part("orx_sight_build_id", "ORX_SIGHT_BUILD_ID", (SIGHT_SRC, SIGHT_HDR, QUERY_HDR),
+                  ()),
 }
-EXTRA_SOURCES = [NPC_QUERY_SRC]
+EXTRA_SOURCES = [NPC_QUERY_SRC, SIGHT_SRC]
 # (SRC first: _build_parts splits it)
 SOURCES = [src for p in PARTS.values() for src in p.sources] + EXTRA_SOURCES
 
@@ -130,13 +136,18 @@ def npc_query_id() -> str:
     return tree_ids()["npc_query"]
 
 
+def sight_id() -> str:
+    """What orx_sight_build_id() of a library built from these sources returns."""
+    return tree_ids()["sight"]
+
+
 def built_ids(path: str = OUT, every: bool = False):
     """``tree_ids``'s dict for the library at `path` ("" for a part it was built
     without; None if it cannot be loaded), read in one child process so this
     one does not map a library that a later build replaces.  The parts
     compiled from sources of their own; with ``every`` also those defined in
     another part's source ("npc", whose id follows its header too) or in
-    EXTRA_SOURCES ("npc_query")."""
+    EXTRA_SOURCES ("npc_query", "sight")."""
     parts = {name: p for name, p in PARTS.items() if every or p.sources}
     code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1])\n"
             "for f in (getattr(L,s,None) for s in sys.argv[2:]):\n"
@@ -196,8 +207,8 @@ def _build_locked(out: str, ids: dict, defines, verbose: bool) -> str:
 # their share of the explicit instantiations, orx_engine.hip "Kernel
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
 # translation unit.  The other SOURCES (orx_view.hip, orx_path.hip,
-# orx_moves.hip and orx_npc_query.hip: small) are one more object each,
-# compiled last.
+# orx_moves.hip, orx_npc_query.hip and orx_sight.hip: small) are one more
+# object each, compiled last.
 NPARTS = 17
 
 

@@ -569,6 +569,56 @@ class BatchedEngine:
                    _ptr(outs[1]) if health else None, self.B, self._stream())
         return (outs[0], outs[1]) if health else outs[0]
 
+    # -- line of sight (include/orx_sight.h) -----------------------------------
+    def sight(self, radius: int, player: int = 0, out=None) -> torch.Tensor:
+        """orx_sight (include/orx_sight.h): which cells of ``view(radius,
+        player)``'s window the player sees through the dungeon's walls, as
+        uint32 [n_games, V] row words: bit ``i`` of ``rows[b, j]`` is window
+        cell (j, i); bits >= V are zero.  A Wall is opaque, everything else
+        transparent; the rule (two digital lines per cell, far walls lit
+        through their floor neighbours) is optimax_rogue_amd.sight's, symmetric
+        among floor cells.  One launch on the current stream from the resident
+        state, no host sync, no state change, no random words.  ``out``: the
+        tensor written and returned.  The host reference is
+        ``sight.pack_rows(sight.visible(self.snapshot(), cfg, player, radius))``."""
+        from .view import check_view_args
+        check_view_args(player, radius)
+        self._require("orx_sight")
+        rows, = self._outs(out, [(torch.uint32, (self.B, 2 * int(radius) + 1))], "one tensor",
+                           align=4)
+        self._call("orx_sight", int(player), int(radius), _ptr(rows), None, None, self.B,
+                   self._stream())
+        return rows
+
+    def seen_view(self, radius: int, player: int = 0, health: bool = False, out=None):
+        """``view(radius, player, health, out)`` under the player's line of
+        sight: orx_view, then orx_sight on its output in place (two launches on
+        the current stream, no host sync; they can be captured in a graph
+        behind a step).  A seen cell is ``code | SIGHT_SEEN`` (bit 6), an
+        unseen one 0; the health plane is 0 where unseen.  The host reference
+        is ``sight.apply(view.render_view(...), sight.visible(...))``."""
+        from .view import check_view_args
+        check_view_args(player, radius)
+        self._require("orx_sight")
+        got = self.view(radius, player=player, health=health, out=out)
+        cells, hp = got if health else (got, None)
+        self._call("orx_sight", int(player), int(radius), None, _ptr(cells), _ptr(hp), self.B,
+                   self._stream())
+        return got
+
+    def sees_other(self, radius: int, player: int = 0) -> torch.Tensor:
+        """bool [n_games]: the other player is on ``player``'s depth, inside
+        its window of this radius, and seen (``sight``'s bit of its cell).
+        Symmetric in the two players at one radius."""
+        rows = self.sight(radius, player=player).view(torch.int32).to(torch.int64)
+        p, q, R = int(player), 1 - int(player), int(radius)
+        i = (self.p_x[q] - self.p_x[p]).to(torch.int64) + R
+        j = (self.p_y[q] - self.p_y[p]).to(torch.int64) + R
+        near = (self.p_depth[p] == self.p_depth[q]) & (i >= 0) & (i <= 2 * R) & (j >= 0) \
+            & (j <= 2 * R)
+        word = rows.gather(1, j.clamp(0, 2 * R).unsqueeze(1)).squeeze(1)
+        return near & (((word >> i.clamp(0, 2 * R)) & 1) != 0)
+
     @property
     def stair_field(self):
         """The bank's staircase distance field on the device, uint16 [L, W, H]

@@ -130,6 +130,23 @@ class VecEnv:
         sync).  Call it after ``step`` (or ``reset``) for that state's view."""
         return self.engine.view(radius, player=player, health=health, out=out)
 
+    def sight(self, radius: int, player: int = 0, out=None) -> torch.Tensor:
+        """uint32 [n_games, 2 * radius + 1] row words: bit ``i`` of row ``j`` is
+        set where ``player`` sees window cell (j, i) of ``view`` through the
+        dungeon's walls (``BatchedEngine.sight``; one launch, no host sync)."""
+        return self.engine.sight(radius, player=player, out=out)
+
+    def seen_view(self, radius: int, player: int = 0, health: bool = False, out=None):
+        """``view`` under the player's line of sight -- partial observability:
+        a seen cell is ``code | SIGHT_SEEN``, an unseen one 0
+        (``BatchedEngine.seen_view``; two launches, no host sync)."""
+        return self.engine.seen_view(radius, player=player, health=health, out=out)
+
+    def sees_other(self, radius: int, player: int = 0) -> torch.Tensor:
+        """bool [n_games]: the other player stands in ``player``'s window and
+        is seen (``BatchedEngine.sees_other``)."""
+        return self.engine.sees_other(radius, player=player)
+
     def path(self, player: int = 0, radius: Optional[int] = None, out=None):
         """``(dist, move)`` of ``player`` (0: the learner) of every game, and
         with a ``radius`` also the uint16 distance ``window``
