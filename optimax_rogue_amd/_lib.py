@@ -120,6 +120,12 @@ _SIGHT = {
     "orx_sight": (_int, [_cfg, _st, i32, i32, vp, vp, vp, i64, vp]),
     "orx_sight_build_id": (_str, []),
 }
+# include/orx_explore.h
+_EXPLORE = {
+    "orx_explore_update": (_int, [_cfg, _st, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "orx_explore_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "orx_explore_build_id": (_str, []),
+}
 
 EXPORTS = tuple(_REQUIRED) + tuple(_OPTIONAL)
 VIEW_EXPORTS = tuple(_VIEW)
@@ -128,6 +134,7 @@ MOVES_EXPORTS = tuple(_MOVES)
 NPC_EXPORTS = tuple(_NPC)
 NPC_QUERY_EXPORTS = tuple(_NPC_QUERY)
 SIGHT_EXPORTS = tuple(_SIGHT)
+EXPLORE_EXPORTS = tuple(_EXPLORE)
 
 
 def load() -> ctypes.CDLL:
@@ -141,7 +148,8 @@ def load() -> ctypes.CDLL:
         raise RuntimeError(f"HIP engine library missing: {LIB_PATH} -- run "
                            "`python -m optimax_rogue_amd.build` first")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC, _NPC_QUERY, _SIGHT):
+    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC, _NPC_QUERY, _SIGHT,
+                  _EXPLORE):
         for name, (restype, argtypes) in table.items():
             if table is _REQUIRED or hasattr(L, name):   # (a missing required symbol raises)
                 fn = getattr(L, name)
@@ -197,3 +205,10 @@ def sight_build_id() -> str:
     sources; "" for a library built before include/orx_sight.h)."""
     L = load()
     return L.orx_sight_build_id().decode() if hasattr(L, "orx_sight_build_id") else ""
+
+
+def explore_build_id() -> str:
+    """orx_explore_build_id() of the loaded library (build.explore_id() of its
+    sources; "" for a library built before include/orx_explore.h)."""
+    L = load()
+    return L.orx_explore_build_id().decode() if hasattr(L, "orx_explore_build_id") else ""

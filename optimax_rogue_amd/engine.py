@@ -121,6 +121,7 @@ class BatchedEngine:
         self.bank = None
         self._stair_field = None   # (the bank's distance field: made by the first path())
         self._pair_field = None    # (the bank's pair table: made by the first seek())
+        self._explore_maps = {}    # (player -> (memory, key): made by the first explore())
         if cfg.layouts is not None:
             from .dungeons import DungeonBank
             bank = DungeonBank(cfg.layouts)
@@ -619,6 +620,113 @@ class BatchedEngine:
         word = rows.gather(1, j.clamp(0, 2 * R).unsqueeze(1)).squeeze(1)
         return near & (((word >> i.clamp(0, 2 * R)) & 1) != 0)
 
+    # -- the remembered map (include/orx_explore.h) ----------------------------
+    def explore_map(self, player: int = 0):
+        """``(memory, key)`` of ``player``'s remembered map: uint32 [n_games, H,
+        WW] with WW = (W + 31) // 32 -- bit ``x % 32`` of ``memory[b, y, x //
+        32]`` is set when the player has seen cell (x, y) on its present depth
+        in the present episode -- and int32 [n_games, 4], {episode, depth, tick,
+        known} (include/orx_explore.h; ``explore.unpack`` gives a bool map).
+        The engine's own tensors, one pair per player, allocated empty at the
+        first use (not under capture) and written by ``explore``.  The map is
+        not part of ``snapshot()``."""
+        from .query import check_player
+        check_player(player)
+        maps = getattr(self, "_explore_maps", None)
+        if maps is None:
+            maps = self._explore_maps = {}
+        if int(player) not in maps:
+            self._require("orx_explore_update")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the remembered map is allocated at the first explore() call: "
+                                   "call explore() (or explore_map()) once before capturing")
+            W, H = int(self.cfg.width), int(self.cfg.height)
+            memory = torch.zeros((self.B, H, (W + 31) // 32), dtype=torch.int32,
+                                 device=self.device).view(torch.uint32)
+            key = torch.full((self.B, 4), -1, dtype=torch.int32, device=self.device)
+            maps[int(player)] = (memory, key)
+        return maps[int(player)]
+
+    def explore(self, radius: int, player: int = 0, view: bool = False, health: bool = False,
+                out=None):
+        """orx_explore_update (include/orx_explore.h): adds what ``player`` (0 /
+        1) of every game sees now in its window of this radius to
+        ``explore_map(player)`` and returns ``gained``, int32 [n_games]: the
+        number of cells newly known -- the usual exploration reward.  A map of
+        another episode or depth (or of a later tick: a reset into the same
+        episode) is cleared first, so a descent and an autoreset need no call.
+        With ``view`` returns ``(gained, cells)`` (and ``health``: ``(gained,
+        cells, health)``): ``view(radius, player)`` as the player remembers it
+        -- a seen cell is ``code | SIGHT_SEEN | EXPLORE_KNOWN``, a known cell
+        out of sight ``tile | EXPLORE_KNOWN`` (occupants and items are not
+        remembered, its health is 0), any other 0.  orx_view when asked, then
+        orx_sight for the row words, then orx_explore_update, all on the
+        current stream with no host sync; no state change, no random words.
+        ``out``: the tensor, or the tuple, written and returned.  The host
+        reference is ``explore.update``."""
+        from .view import check_view_args
+        check_view_args(player, radius)
+        if health and not view:
+            raise ValueError("health=True needs view=True")
+        self._require("orx_explore_update")
+        self._require("orx_sight")
+        V = 2 * int(radius) + 1
+        specs = [(torch.int32, (self.B,))] + [(torch.uint8, (self.B, V, V))] * (view + (view and health))
+        outs = self._outs(out, specs, "gained, (gained, cells) with view=True, or (gained, cells, "
+                          "health) with health=True too",
+                          distinct=("gained", "cells", "health")[:len(specs)] if view else None)
+        if outs[0].data_ptr() % 4:
+            raise ValueError("out: gained must be 4-byte aligned")
+        memory, key = self.explore_map(player)
+        cells = outs[1] if view else None
+        hp = outs[2] if view and health else None
+        if view:
+            self.view(radius, player=player, health=health, out=(cells, hp) if health else cells)
+        rows = self.sight(radius, player=player)
+        self._call("orx_explore_update", int(player), int(radius), _ptr(rows), _ptr(memory),
+                   _ptr(key), _ptr(outs[0]), _ptr(cells), _ptr(hp), self.B, self._stream())
+        return tuple(outs) if view else outs[0]
+
+    def explore_seek(self, player: int = 0, out=None):
+        """orx_explore_seek (include/orx_explore.h): how many moves ``player``
+        (0 / 1) of every game is from the nearest frontier cell of its
+        remembered map -- a known Ground cell with a neighbour it has not seen
+        -- and from the nearest StaircaseDown it has seen, and the move that
+        gets one step closer.  Returns ``(dist, move, target)``: int32, int8 and
+        int32 [n_games, SEEK_COLS = 4], columns EXPLORE_FRONTIER,
+        EXPLORE_STAIRS and two of padding; ``dist`` is SEEK_ABSENT (-2) where
+        the column has no target (nothing left to explore; no staircase seen
+        yet) or the map is not of this state, SEEK_UNREACHABLE (-1) where no
+        target can be walked to; ``target`` the flat cell ``x * H + y``.  Every
+        shortest walk to the nearest frontier cell passes only known cells.
+        One launch, no host sync, no state change; with a bank the first call
+        also builds ``pair_field``.  ``out``: a ``(dist, move, target)`` tuple
+        written and returned.  The host reference is ``explore.seek``."""
+        from .path import SEEK_COLS
+        from .query import check_player
+        check_player(player)
+        self._require("orx_explore_seek")
+        shape = (self.B, SEEK_COLS)
+        outs = self._outs(out, [(torch.int32, shape), (torch.int8, shape), (torch.int32, shape)],
+                          "(dist, move, target)", align=16, distinct=("dist", "move", "target"))
+        if int(self.cfg.width) * int(self.cfg.height) > 65536:
+            raise ValueError("explore_seek needs width * height <= 65536 (a flat cell in 16 bits)")
+        memory, key = self.explore_map(player)
+        pairs = self.pair_field
+        self._call("orx_explore_seek", _ptr(pairs), int(player), _ptr(memory), _ptr(key),
+                   _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), self.B, self._stream())
+        return tuple(outs)
+
+    def explore_forget(self, player: Optional[int] = None) -> None:
+        """Clears the remembered map of ``player`` (both players' when None):
+        all-zero memory, the key -1 (two fills on the current stream)."""
+        if player not in (None, 0, 1):
+            raise ValueError(f"player must be None, 0 or 1, got {player!r}")
+        for p, (memory, key) in (getattr(self, "_explore_maps", None) or {}).items():
+            if player is None or p == int(player):
+                memory.view(torch.int32).zero_()
+                key.fill_(-1)
+
     @property
     def stair_field(self):
         """The bank's staircase distance field on the device, uint16 [L, W, H]
@@ -984,6 +1092,7 @@ class BatchedEngine:
             dst.copy_(torch.from_numpy(a.reshape(dst.shape)))
         if self.npc_grid is not None and ("npc_pos" in snap or "npc_alive" in snap):
             self._rebuild_npc_grid()
+        self.explore_forget()   # (a remembered map is of the state it was made in)
 
     def _rebuild_npc_grid(self) -> None:
         """Dense NPCs: the occupancy grid (slot + 1 per cell of the NPC depth)

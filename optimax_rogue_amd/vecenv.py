@@ -195,6 +195,42 @@ class VecEnv:
         dist_after)`` on the steps where both are positive."""
         return self.engine.seek(player=player, out=out)
 
+    # the remembered map (include/orx_explore.h): sight plus memory
+    def explore(self, radius: int, player: int = 0, view: bool = False, health: bool = False,
+                out=None):
+        """Adds what ``player`` sees now to the map it remembers and returns
+        ``gained`` int32 [n_games], the number of cells newly known (the
+        exploration reward); with ``view`` also the window as the player
+        remembers it (``BatchedEngine.explore``; no host sync).  Call it after
+        every ``step`` (and ``reset``): descents and autoresets clear the map
+        by themselves."""
+        return self.engine.explore(radius, player=player, view=view, health=health, out=out)
+
+    def explore_seek(self, player: int = 0, out=None):
+        """``(dist, move, target)`` of ``player``, [n_games, 4] each: how many
+        moves away the nearest edge of its remembered map (column
+        EXPLORE_FRONTIER) and the nearest staircase it has seen (column
+        EXPLORE_STAIRS) are, the move that gets one step closer and the
+        target's flat cell (``BatchedEngine.explore_seek``; one launch)."""
+        return self.engine.explore_seek(player=player, out=out)
+
+    def explore_forget(self, player: Optional[int] = None) -> None:
+        """Clears the remembered map of ``player`` (None: of both)."""
+        self.engine.explore_forget(player)
+
+    def explore_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games], ready as ``actions``: the move toward the nearest
+        edge of what ``player`` knows where one is left, else toward the
+        nearest staircase it has seen, else Stay -- the scripted baseline of
+        the partially observable game.  It uses the layout only where the
+        player has seen it (the walk to the nearest frontier cell passes known
+        cells only); call ``explore`` first in every state."""
+        from .enums import Move
+        from .explore import EXPLORE_FRONTIER as F, EXPLORE_STAIRS as S
+        dist, move, _ = self.engine.explore_seek(player=player)
+        stairs = torch.where(dist[:, S] > 0, move[:, S], int(Move.Stay))
+        return torch.where(dist[:, F] > 0, move[:, F], stairs)
+
     def hunt_moves(self, player: int = 0) -> torch.Tensor:
         """int8 [n_games]: the move that takes ``player`` one step along a
         shortest walk to the other player where one exists, else
