@@ -4,7 +4,7 @@ per-tick updater (reference: optimax_rogue/logic + optimax_rogue/game).
 Host side is Python; the tick, reset and bot policies are HIP kernels for
 gfx950 in liborx.so, reached through the C-ABI declared in include/orx.h.
 """
-from . import explore, moves, npc_query, path, sight
+from . import explore, moves, npc_query, path, route, sight
 from .config import EnvConfig
 from .dungeons import DungeonBank
 from .enums import (CombatFlag, DungeonDespawningStrategy, Move, NpcPolicy, OBS_FIELDS, Policy,
@@ -12,7 +12,7 @@ from .enums import (CombatFlag, DungeonDespawningStrategy, Move, NpcPolicy, OBS_
 
 __all__ = ["EnvConfig", "DungeonBank", "Move", "UpdateResult", "DungeonDespawningStrategy", "Tile", "CombatFlag",
            "StartMode", "Policy", "NpcPolicy", "OBS_FIELDS", "BatchedEngine", "StreamShardedEngine", "BatchedUpdater",
-           "VecEnv", "render_view", "path", "moves", "npc_query", "sight", "explore"]
+           "VecEnv", "render_view", "path", "moves", "npc_query", "sight", "explore", "route"]
 
 
 def __getattr__(name):

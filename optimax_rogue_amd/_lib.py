@@ -126,6 +126,12 @@ _EXPLORE = {
     "orx_explore_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, vp, vp, i64, vp]),
     "orx_explore_build_id": (_str, []),
 }
+# include/orx_route.h
+_ROUTE = {
+    "orx_route_planes": (_int, [_cfg, vp, vp, vp]),
+    "orx_route": (_int, [_cfg, _st, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "orx_route_build_id": (_str, []),
+}
 
 EXPORTS = tuple(_REQUIRED) + tuple(_OPTIONAL)
 VIEW_EXPORTS = tuple(_VIEW)
@@ -135,6 +141,7 @@ NPC_EXPORTS = tuple(_NPC)
 NPC_QUERY_EXPORTS = tuple(_NPC_QUERY)
 SIGHT_EXPORTS = tuple(_SIGHT)
 EXPLORE_EXPORTS = tuple(_EXPLORE)
+ROUTE_EXPORTS = tuple(_ROUTE)
 
 
 def load() -> ctypes.CDLL:
@@ -149,7 +156,7 @@ def load() -> ctypes.CDLL:
                            "`python -m optimax_rogue_amd.build` first")
     L = ctypes.CDLL(LIB_PATH)
     for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC, _NPC_QUERY, _SIGHT,
-                  _EXPLORE):
+                  _EXPLORE, _ROUTE):
         for name, (restype, argtypes) in table.items():
             if table is _REQUIRED or hasattr(L, name):   # (a missing required symbol raises)
                 fn = getattr(L, name)
@@ -212,3 +219,10 @@ def explore_build_id() -> str:
     sources; "" for a library built before include/orx_explore.h)."""
     L = load()
     return L.orx_explore_build_id().decode() if hasattr(L, "orx_explore_build_id") else ""
+
+
+def route_build_id() -> str:
+    """orx_route_build_id() of the loaded library (build.route_id() of its
+    sources; "" for a library built before include/orx_route.h)."""
+    L = load()
+    return L.orx_route_build_id().decode() if hasattr(L, "orx_route_build_id") else ""

@@ -52,6 +52,9 @@ SIGHT_HDR = os.path.join(ROOT, "include", "orx_sight.h")
 # the map a player remembers and the way to its edge (orx_explore_*): one more object
 EXPLORE_SRC = os.path.join(PKG_DIR, "csrc", "orx_explore.hip")
 EXPLORE_HDR = os.path.join(ROOT, "include", "orx_explore.h")
+# walking distances over the remembered map (orx_route*): one more object
+ROUTE_SRC = os.path.join(PKG_DIR, "csrc", "orx_route.hip")
+ROUTE_HDR = os.path.join(ROOT, "include", "orx_route.h")
 OUT = os.path.join(PKG_DIR, "liborx.so")
 ARCH = os.environ.get("ORX_OFFLOAD_ARCH", "gfx950")
 AB_LIBS = os.path.join(ROOT, "tools", "ab_libs")
@@ -93,8 +96,11 @@ PARTS = {
     # (the same)
     "explore": Part("orx_explore_build_id", "ORX_EXPLORE_BUILD_ID",
                     (EXPLORE_SRC, EXPLORE_HDR, QUERY_HDR), ()),
+    # (the same)
+    "route": Part("orx_route_build_id", "ORX_ROUTE_BUILD_ID", (ROUTE_SRC, ROUTE_HDR, QUERY_HDR),
+                  ()),
 }
-EXTRA_SOURCES = [NPC_QUERY_SRC, SIGHT_SRC, EXPLORE_SRC]
+EXTRA_SOURCES = [NPC_QUERY_SRC, SIGHT_SRC, EXPLORE_SRC, ROUTE_SRC]
 # (SRC first: _build_parts splits it)
 SOURCES = [src for p in PARTS.values() for src in p.sources] + EXTRA_SOURCES
 
@@ -152,13 +158,18 @@ def explore_id() -> str:
     return tree_ids()["explore"]
 
 
+def route_id() -> str:
+    """What orx_route_build_id() of a library built from these sources returns."""
+    return tree_ids()["route"]
+
+
 def built_ids(path: str = OUT, every: bool = False):
     """``tree_ids``'s dict for the library at `path` ("" for a part it was built
     without; None if it cannot be loaded), read in one child process so this
     one does not map a library that a later build replaces.  The parts
     compiled from sources of their own; with ``every`` also those defined in
     another part's source ("npc", whose id follows its header too) or in
-    EXTRA_SOURCES ("npc_query", "sight", "explore")."""
+    EXTRA_SOURCES ("npc_query", "sight", "explore", "route")."""
     parts = {name: p for name, p in PARTS.items() if every or p.sources}
     code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1])\n"
             "for f in (getattr(L,s,None) for s in sys.argv[2:]):\n"
@@ -218,8 +229,8 @@ def _build_locked(out: str, ids: dict, defines, verbose: bool) -> str:
 # their share of the explicit instantiations, orx_engine.hip "Kernel
 # instances"), then linked -- about a minute on 8 cores instead of ~6 for one
 # translation unit.  The other SOURCES (orx_view.hip, orx_path.hip,
-# orx_moves.hip, orx_npc_query.hip, orx_sight.hip and orx_explore.hip: small) are one more
-# object each, compiled last.
+# orx_moves.hip, orx_npc_query.hip, orx_sight.hip, orx_explore.hip and orx_route.hip: small)
+# are one more object each, compiled last.
 NPARTS = 17
 
 

@@ -122,6 +122,7 @@ class BatchedEngine:
         self._stair_field = None   # (the bank's distance field: made by the first path())
         self._pair_field = None    # (the bank's pair table: made by the first seek())
         self._explore_maps = {}    # (player -> (memory, key): made by the first explore())
+        self._route_planes = None  # (the bank's bit planes: made by the first explore_route())
         if cfg.layouts is not None:
             from .dungeons import DungeonBank
             bank = DungeonBank(cfg.layouts)
@@ -726,6 +727,83 @@ class BatchedEngine:
             if player is None or p == int(player):
                 memory.view(torch.int32).zero_()
                 key.fill_(-1)
+
+    # -- walks over the remembered map (include/orx_route.h) -------------------
+    @property
+    def route_planes(self):
+        """The bank's Ground and StaircaseDown bits on the device, uint32 [L, 2,
+        H, WW] in the remembered map's layout (orx_route_planes,
+        include/orx_route.h; ``route.planes`` is its host twin), packed by one
+        launch at the first use.  None without a bank."""
+        if self.bank is None:
+            return None
+        if getattr(self, "_route_planes", None) is None:
+            self._require("orx_route_planes")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the bank's bit planes are packed at the first explore_route() "
+                                   "call: call explore_route() (or read route_planes) once before "
+                                   "capturing")
+            W, H = int(self.cfg.width), int(self.cfg.height)
+            planes = torch.empty((len(self.bank), 2, H, (W + 31) // 32), dtype=torch.int32,
+                                 device=self.device).view(torch.uint32)
+            with torch.cuda.device(self.device):
+                code = self.lib.orx_route_planes(self._pcfg, _ptr(self.bank_tiles), _ptr(planes),
+                                                 self._stream())
+            _lib.check("orx_route_planes", code)
+            self._route_planes = planes
+        return self._route_planes
+
+    def explore_route(self, player: int = 0, goal=None, out=None):
+        """orx_route (include/orx_route.h): how many moves ``player`` (0 / 1)
+        of every game is from the nearest frontier cell of its remembered map,
+        from the nearest StaircaseDown it has seen and from the cell
+        ``goal[b]``, walking through cells it KNOWS only, and the move that
+        gets one step closer.  Returns ``(dist, move, target)``: int32, int8
+        and int32 [n_games, SEEK_COLS = 4], columns ROUTE_FRONTIER,
+        ROUTE_STAIRS, ROUTE_GOAL and one of padding, in ``explore_seek``'s
+        conventions (SEEK_ABSENT, SEEK_UNREACHABLE; ``target`` the flat cell
+        ``x * H + y``).  ``goal``: an integer tensor [n_games] of flat cells
+        (cast to int32 on the device), or None -- the column is then absent,
+        as where a goal is outside ``[0, W * H)``; a goal the player has not
+        seen, or a Wall, is unreachable.  A breadth-first search over the map
+        itself: no pair table, so it runs on every bank the engine accepts.
+        One launch, no host sync, no state change; with a bank the first call
+        also packs ``route_planes``.  ``out``: a ``(dist, move, target)`` tuple
+        written and returned.  The host reference is ``route.route``."""
+        from .path import SEEK_COLS
+        from .query import check_player
+        check_player(player)
+        self._require("orx_route")
+        shape = (self.B, SEEK_COLS)
+        outs = self._outs(out, [(torch.int32, shape), (torch.int8, shape), (torch.int32, shape)],
+                          "(dist, move, target)", align=16, distinct=("dist", "move", "target"))
+        if int(self.cfg.width) * int(self.cfg.height) > 65536:
+            raise ValueError("explore_route needs width * height <= 65536 (a flat cell in 16 bits)")
+        if goal is not None:
+            if not isinstance(goal, torch.Tensor) or goal.dtype not in (
+                    torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) \
+                    or tuple(goal.shape) != (self.B,):
+                raise ValueError(f"goal must be an integer tensor of shape ({self.B},)")
+            if goal.device != self.device:
+                raise ValueError(f"goal is on {goal.device}, the engine on {self.device}")
+            goal = goal.to(torch.int32).contiguous()
+        memory, key = self.explore_map(player)
+        planes = self.route_planes
+        self._call("orx_route", _ptr(planes), int(player), _ptr(memory), _ptr(key), _ptr(goal),
+                   _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), self.B, self._stream())
+        return tuple(outs)
+
+    def explore_route_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games], ready as ``actions``: ``explore_route``'s frontier
+        move where a frontier cell is left to walk to, else its stairs move
+        where a known walk leads to a staircase, else Stay -- the explorer
+        that needs no pair table and never leaves what the player knows
+        (``route.router_moves``).  Call ``explore`` first in every state."""
+        from .enums import Move
+        from .route import ROUTE_FRONTIER as F, ROUTE_STAIRS as S
+        dist, move, _ = self.explore_route(player=player)
+        stairs = torch.where(dist[:, S] > 0, move[:, S], int(Move.Stay))
+        return torch.where(dist[:, F] > 0, move[:, F], stairs)
 
     @property
     def stair_field(self):

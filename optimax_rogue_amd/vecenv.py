@@ -231,6 +231,25 @@ class VecEnv:
         stairs = torch.where(dist[:, S] > 0, move[:, S], int(Move.Stay))
         return torch.where(dist[:, F] > 0, move[:, F], stairs)
 
+    def explore_route(self, player: int = 0, goal=None, out=None):
+        """``(dist, move, target)`` of ``player``, [n_games, 4] each: how many
+        moves away the nearest edge of its remembered map (column
+        ROUTE_FRONTIER), the nearest staircase it has seen (ROUTE_STAIRS) and
+        the cell ``goal[b]`` (ROUTE_GOAL; ``goal`` an integer tensor of flat
+        cells ``x * H + y`` or None) are along cells it KNOWS, and the move
+        that gets one step closer (``BatchedEngine.explore_route``; one launch,
+        no pair table).  The stairs distance is an honest reward potential:
+        it never uses a cell the player has not seen."""
+        return self.engine.explore_route(player=player, goal=goal, out=out)
+
+    def explore_route_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games], ready as ``actions``: ``explore_moves`` by a search
+        over the remembered map itself -- toward the nearest edge of what
+        ``player`` knows, else toward a staircase it knows a way to, else Stay
+        (``BatchedEngine.explore_route_moves``).  It needs no pair table, so it
+        runs on banks of any size; call ``explore`` first in every state."""
+        return self.engine.explore_route_moves(player=player)
+
     def hunt_moves(self, player: int = 0) -> torch.Tensor:
         """int8 [n_games]: the move that takes ``player`` one step along a
         shortest walk to the other player where one exists, else
