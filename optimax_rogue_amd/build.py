@@ -39,6 +39,8 @@ PATH_HDR = os.path.join(ROOT, "include", "orx_path.h")
 MOVES_SRC = os.path.join(PKG_DIR, "csrc", "orx_moves.hip")
 MOVES_HDR = os.path.join(ROOT, "include", "orx_moves.h")
 QUERY_HDR = os.path.join(PKG_DIR, "csrc", "orx_query.h")
+# the seek-shaped rules that path, npc_query, explore and route share (internal)
+SEEK_HDR = os.path.join(PKG_DIR, "csrc", "orx_seek.h")
 PLAN_HDR = os.path.join(PKG_DIR, "csrc", "orx_plan.h")   # the engine's launch plan (host side)
 # the tick with the NPCs' moves from the caller (orx_npc_*): defined in the
 # engine's source (it needs the moving-NPC tick), declared in a header of its own
@@ -80,8 +82,8 @@ Part = namedtuple("Part", "symbol macro files sources")
 PARTS = {
     "engine": Part("orx_build_id", "ORX_BUILD_ID", (SRC, HDR, VIEW_SRC, VIEW_HDR, QUERY_HDR,
                                                      PLAN_HDR), (SRC, VIEW_SRC)),
-    "path": Part("orx_path_build_id", "ORX_PATH_BUILD_ID", (PATH_SRC, PATH_HDR, QUERY_HDR),
-                 (PATH_SRC,)),
+    "path": Part("orx_path_build_id", "ORX_PATH_BUILD_ID", (PATH_SRC, PATH_HDR, QUERY_HDR,
+                                                               SEEK_HDR), (PATH_SRC,)),
     "moves": Part("orx_moves_build_id", "ORX_MOVES_BUILD_ID", (MOVES_SRC, MOVES_HDR, QUERY_HDR),
                   (MOVES_SRC,)),
     "npc": Part("orx_npc_build_id", "ORX_NPC_BUILD_ID", (NPC_HDR, SRC), ()),
@@ -89,16 +91,16 @@ PARTS = {
     # parts a caller sees without it stay engine, path and moves; its object is
     # named in EXTRA_SOURCES)
     "npc_query": Part("orx_npc_query_build_id", "ORX_NPC_QUERY_BUILD_ID",
-                      (NPC_QUERY_SRC, NPC_QUERY_HDR, QUERY_HDR), ()),
+                      (NPC_QUERY_SRC, NPC_QUERY_HDR, QUERY_HDR, SEEK_HDR), ()),
     # (the same: its object is named in EXTRA_SOURCES)
     "sight": Part("orx_sight_build_id", "ORX_SIGHT_BUILD_ID", (SIGHT_SRC, SIGHT_HDR, QUERY_HDR),
                   ()),
     # (the same)
     "explore": Part("orx_explore_build_id", "ORX_EXPLORE_BUILD_ID",
-                    (EXPLORE_SRC, EXPLORE_HDR, QUERY_HDR), ()),
+                    (EXPLORE_SRC, EXPLORE_HDR, QUERY_HDR, SEEK_HDR), ()),
     # (the same)
-    "route": Part("orx_route_build_id", "ORX_ROUTE_BUILD_ID", (ROUTE_SRC, ROUTE_HDR, QUERY_HDR),
-                  ()),
+    "route": Part("orx_route_build_id", "ORX_ROUTE_BUILD_ID", (ROUTE_SRC, ROUTE_HDR, QUERY_HDR,
+                                                                  SEEK_HDR), ()),
 }
 EXTRA_SOURCES = [NPC_QUERY_SRC, SIGHT_SRC, EXPLORE_SRC, ROUTE_SRC]
 # (SRC first: _build_parts splits it)

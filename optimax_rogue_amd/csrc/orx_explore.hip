@@ -2,9 +2,12 @@
 // (include/orx_explore.h) for gfx950.
 //
 // Two kernels, neither of which needs the tick machinery: only orx.h's structs,
-// the queries' shared header and the host side's error path.  The room distance
-// and the first-move rule are orx_path_seek's, restated here (as
-// orx_npc_query.hip restates them) so that orx_path.hip stays what it is.
+// the queries' shared headers and the host side's error path.  The room distance
+// is orx_seek.h's, as are the key's rule, the wave's minimum, the dist / move
+// stores and the host side's refusals.  seek_kernel keeps its own Dungeon (the
+// tile, the table lookup by flat cell, the first-move test over eight lanes)
+// and its frontier words inline: lifted into Seeker and frontier_bits they cost
+// the kernel 1-2%.
 //
 // update_kernel.  A THREAD IS A WINDOW ROW.  A workgroup of 256 threads takes 64
 // consecutive games (their maps, row words and planes are contiguous), and
@@ -37,22 +40,17 @@
 // Plain C++ and vector stores only.
 #include "../../include/orx_explore.h"
 #include "orx_query.h"
+#include "orx_seek.h"
 
 namespace orx_explore_dev {
 
 using namespace orx_query;
 
 constexpr int kGames = 64;  // games per workgroup of update_kernel
-constexpr uint32_t kFar = ORX_PATH_UNREACHABLE;
+constexpr uint32_t kFar = ORX_PATH_UNREACHABLE;  // the distance part of a packed word without a walk
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // a column without a target (above every packed word)
 
 enum { H_PX, H_PY, H_VALID, H_KNOWN, H_GAIN, kHdr };  // per game ([kHdr][G] int32 in LDS)
-
-// whether key row k is valid for a state (the header's rule)
-__device__ __forceinline__ bool key_valid(const int4 k, int32_t episode, int32_t depth,
-                                          int32_t tick) {
-  return k.w >= 0 && k.x == episode && k.y == depth && k.z <= tick;
-}
 
 // a coordinate held to where the window arithmetic cannot overflow
 __device__ __forceinline__ int tame(int v) { return v < -64 ? -64 : v > (1 << 20) ? (1 << 20) : v; }
@@ -70,33 +68,13 @@ struct UpdateArgs {
   uint32_t inv_vv, inv_v;  // (R, G, inv_vv, inv_v: a Window)
 };
 
-// bits 0..3 of n -> all bits of bytes 0..3
-__device__ __forceinline__ uint32_t spread4(uint32_t n) {
-  return (((n & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;
-}
-
 // four view codes under four seen and four known bits (seen cells are known)
 __device__ __forceinline__ uint32_t remember4(uint32_t w, uint32_t seen, uint32_t known) {
-  const uint32_t s = spread4(seen), k = spread4(known);
+  const uint32_t s = spread4(seen) * 0xFFu, k = spread4(known) * 0xFFu;
   constexpr uint32_t kSeen = (ORX_SIGHT_SEEN | ORX_EXPLORE_KNOWN) * 0x01010101u;
   constexpr uint32_t kKnown = ORX_EXPLORE_KNOWN * 0x01010101u;
   constexpr uint32_t kTile = ORX_VIEW_TILE_MASK * 0x01010101u;
   return ((w | kSeen) & s) | (((w & kTile) | kKnown) & k & ~s);
-}
-
-// bits [i, i + 16) of the window's flat cell sequence starting at row `row`,
-// column `i`, out of per-row words: the cells run over a row's end into the next
-__device__ __forceinline__ uint32_t gather16(const uint32_t* words, int row, int i, int V) {
-  uint32_t bits = 0;
-  int filled = 0;
-  while (filled < 16) {
-    const int take = V - i < 16 - filled ? V - i : 16 - filled;
-    bits |= ((words[row] >> i) & ((1u << take) - 1u)) << filled;
-    filled += take;
-    i = 0;
-    ++row;
-  }
-  return bits;
 }
 
 // plane[0 .. n) (a workgroup's cells, in place).  kCells: the view codes, else
@@ -119,7 +97,8 @@ __device__ __forceinline__ void remember_plane(const uint32_t* seen, const uint3
       w.z = remember4(w.z, s >> 8, k >> 8);
       w.w = remember4(w.w, s >> 12, k >> 12);
     } else {
-      w.x &= spread4(s), w.y &= spread4(s >> 4), w.z &= spread4(s >> 8), w.w &= spread4(s >> 12);
+      w.x &= spread4(s) * 0xFFu, w.y &= spread4(s >> 4) * 0xFFu;
+      w.z &= spread4(s >> 8) * 0xFFu, w.w &= spread4(s >> 12) * 0xFFu;
     }
     q[v] = w;
   }
@@ -134,13 +113,6 @@ __device__ __forceinline__ void remember_plane(const uint32_t* seen, const uint3
     else
       plane[c] = (uint8_t)(s ? w : 0u);
   }
-}
-
-// the window columns that lie in the grid's x range, as row-word bits
-__device__ __forceinline__ uint32_t grid_columns(int px, int W, int R, int V) {
-  const int i0 = R - px, i1 = W - 1 - px + R;  // window columns of x = 0 and x = W - 1
-  const int lo = i0 > 0 ? i0 : 0, hi = i1 < V - 1 ? i1 : V - 1;
-  return lo <= hi ? ((2u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
 }
 
 __global__ __launch_bounds__(kBlock) void update_kernel(const UpdateArgs a) {
@@ -243,10 +215,11 @@ struct SeekArgs {
   int32_t* target;
   int64_t B;
   int32_t W, H, WW, L, player, G;
-  uint32_t inv_h;  // 2^32 / H + 1: __umulhi(c, inv_h) = c / H for c < 2^16
+  uint32_t inv_h;  // recip(H): __umulhi(c, inv_h) = c / H for a flat cell c
 };
 
-// One game's viewer on its dungeon: the tiles and the distances (orx_path_seek's).
+// One game's viewer on its dungeon: the tiles and the distances, kFar where
+// there is no walk.
 struct Dungeon {
   int W, H, sx, sy;
   const uint16_t* table;  // pairs[layout], or nullptr: the closed form
@@ -262,36 +235,17 @@ struct Dungeon {
     if (cx == 0 || cx == W - 1 || cy == 0 || cy == H - 1) return ORX_TILE_WALL;
     return cx == sx && cy == sy ? ORX_TILE_STAIRCASE_DOWN : ORX_TILE_GROUND;
   }
-  // the walking distance between two cells of the grid, kFar where there is none
-  __device__ __forceinline__ uint32_t room(int ax, int ay, int tx, int ty) const {
-    // border Wall; an open interior at least two cells wide, so only a
-    // staircase strictly between two cells of one row or column costs a
-    // detour, of two moves
-    if (ax < 1 || ax > W - 2 || ay < 1 || ay > H - 2 || tx < 1 || tx > W - 2 || ty < 1 || ty > H - 2)
-      return kFar;
-    const int dx = ax - tx, dy = ay - ty;
-    uint32_t d = (uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy));
-    if (dx == 0 && sx == ax && (ay < sy) != (ty < sy) && sy != ay && sy != ty) d += 2u;
-    if (dy == 0 && sy == ay && (ax < sx) != (tx < sx) && sx != ax && sx != tx) d += 2u;
-    return d;
+  // the closed form's distance between two cells of the grid
+  __device__ __forceinline__ uint32_t closed(int ax, int ay, int tx, int ty) const {
+    return room<kFar>(W, H, sx, sy, ax, ay, tx, ty);
   }
   // ... from cell (ax, ay) to the cell whose table row is `row` (flat cell tc)
   __device__ __forceinline__ uint32_t between(int ax, int ay, int tc, int tx, int ty) const {
-    if (!table) return room(ax, ay, tx, ty);
+    if (!table) return closed(ax, ay, tx, ty);
     const uint32_t v = table[(size_t)tc * (size_t)(W * H) + (size_t)(ax * H + ay)];
     return v >= kFar ? kFar : v;
   }
 };
-
-// the least of a packed word over the wave
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
   extern __shared__ uint4 smem[];
@@ -350,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
         } else {
           continue;
         }
-        uint32_t d = row ? (uint32_t)row[c] : s.room(x, y, cx, cy);
+        uint32_t d = row ? (uint32_t)row[c] : s.closed(x, y, cx, cy);
         d = d >= kFar ? kFar : d;
         const uint32_t packed = d << 16 | (uint32_t)c;
         best[col] = packed < best[col] ? packed : best[col];
@@ -383,9 +337,8 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
     move[col] = nib ? (uint32_t)(ORX_MOVE_UP + __builtin_ctz(nib)) : (uint32_t)ORX_MOVE_STAY;
     target[col] = p == kNone ? 0xFFFFFFFFu : (p & 0xFFFFu);
   }
-  const uint32_t absent = (uint32_t)ORX_SEEK_ABSENT, stay = ORX_MOVE_STAY;
-  if (a.dist) reinterpret_cast<uint4*>(a.dist)[b] = make_uint4(dist[0], dist[1], absent, absent);
-  if (a.move) reinterpret_cast<uint32_t*>(a.move)[b] = move[0] | move[1] << 8 | stay << 16 | stay << 24;
+  store_seek_rows(a.dist, a.move, b, dist[0], dist[1], (uint32_t)ORX_SEEK_ABSENT, move[0], move[1],
+                  ORX_MOVE_STAY);
   if (a.target)
     reinterpret_cast<uint4*>(a.target)[b] = make_uint4(target[0], target[1], 0xFFFFFFFFu, 0xFFFFFFFFu);
 }
@@ -397,16 +350,6 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
 #endif
 
 extern "C" const char* orx_explore_build_id(void) { return ORX_EXPLORE_BUILD_ID; }
-
-namespace {
-// what both entry points read of the state besides p_x and p_y
-int check_clock(const orx_state_t* st) {
-  if (!st->p_depth || !st->tick || !st->episode)
-    return orx_dev::fail(ORX_EINVAL, "a required state pointer is NULL");
-  return ORX_OK;
-}
-inline bool misaligned(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) & (n - 1); }
-}  // namespace
 
 extern "C" int orx_explore_update(const orx_cfg_t* cfg, const orx_state_t* st, int32_t player,
                                   int32_t radius, const uint32_t* rows, uint32_t* memory,
@@ -423,9 +366,9 @@ extern "C" int orx_explore_update(const orx_cfg_t* cfg, const orx_state_t* st, i
   if (misaligned(rows, 4) || misaligned(memory, 4) || misaligned(gained, 4) || misaligned(key, 16))
     return fail(ORX_EINVAL,
                 "orx_explore_update: rows, memory and gained must be 4-byte, key 16-byte aligned");
-  if ((r = check_games("orx_explore_update", n_games)) || (r = check_state(cfg, st, 0)) ||
-      (r = check_clock(st)))
-    return r;
+  if ((r = check_games("orx_explore_update", n_games)) || (r = check_state(cfg, st, 0))) return r;
+  if (!st->p_depth || !st->tick || !st->episode)
+    return fail(ORX_EINVAL, "a required state pointer is NULL");
 
   UpdateArgs a;
   a.p_x = st->p_x, a.p_y = st->p_y, a.p_depth = st->p_depth;
@@ -435,11 +378,10 @@ extern "C" int orx_explore_update(const orx_cfg_t* cfg, const orx_state_t* st, i
   a.B = n_games;
   a.W = cfg->width, a.H = cfg->height, a.WW = (cfg->width + 31) / 32;
   a.player = player;
-  const int G = kGames, V = 2 * radius + 1, VV = V * V;
-  a.R = radius, a.G = G;
-  a.inv_vv = (uint32_t)(0x100000000ULL / (uint64_t)VV) + 1u;
-  a.inv_v = (uint32_t)(0x100000000ULL / (uint64_t)V) + 1u;
-  const size_t lds = sizeof(uint32_t) * (size_t)G * (size_t)(2 * V + kHdr);
+  const Window win = Window::fit(radius, 0, kGames);  // (no tiles: always kGames games)
+  const int G = win.G;
+  a.R = win.R, a.G = G, a.inv_vv = win.inv_vv, a.inv_v = win.inv_v;
+  const size_t lds = sizeof(uint32_t) * (size_t)G * (size_t)(2 * win.V + kHdr);
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   hipLaunchKernelGGL(update_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, a);
   return orx_dev::launch_status("orx_explore_update");
@@ -453,19 +395,9 @@ extern "C" int orx_explore_seek(const orx_cfg_t* cfg, const orx_state_t* st, con
   using orx_dev::fail;
   int r;
   if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_explore_seek", player))) return r;
-  if (!memory || !key) return fail(ORX_EINVAL, "orx_explore_seek: memory or key is NULL");
-  if (misaligned(memory, 4) || misaligned(key, 16))
-    return fail(ORX_EINVAL, "orx_explore_seek: memory must be 4-byte and key 16-byte aligned");
-  if (!dist && !move && !target)
-    return fail(ORX_EINVAL, "orx_explore_seek: dist, move and target are all NULL");
-  // (a row is one vector store)
-  if (misaligned(dist, 16) || misaligned(move, 4) || misaligned(target, 16))
-    return fail(ORX_EINVAL,
-                "orx_explore_seek: dist and target must be 16-byte and move 4-byte aligned");
-  if ((r = check_games("orx_explore_seek", n_games))) return r;
-  if ((int64_t)cfg->width * cfg->height > 65536)
-    return fail(ORX_EINVAL, "orx_explore_seek: a flat cell must fit 16 bits (W * H <= 65536)");
-  if ((r = check_state(cfg, st, kStairsNoBank | kBank)) || (r = check_clock(st))) return r;
+  if ((r = check_memory_rows("orx_explore_seek", memory, key, dist, move, target)) ||
+      (r = check_memory_query("orx_explore_seek", cfg, st, n_games)))
+    return r;
   if (cfg->n_layouts > 0 && !pairs)
     return fail(ORX_EINVAL, "orx_explore_seek: n_layouts > 0 needs pairs");
 
@@ -479,13 +411,11 @@ extern "C" int orx_explore_seek(const orx_cfg_t* cfg, const orx_state_t* st, con
   a.B = n_games;
   a.W = cfg->width, a.H = cfg->height, a.WW = (cfg->width + 31) / 32, a.L = cfg->n_layouts;
   a.player = player;
-  a.inv_h = (uint32_t)(0x100000000ULL / (uint64_t)cfg->height) + 1u;
-  // a wave per game, four to a workgroup while their maps fit 32 KiB of LDS
+  a.inv_h = recip(cfg->height);
+  // a wave per game, its map in LDS
   // (W * H <= 65536 and W >= 4: one map is at most 64 KiB, the default limit)
   const size_t map_bytes = sizeof(uint32_t) * (size_t)a.H * (size_t)a.WW;
-  int G = 4;
-  while (G > 1 && (size_t)G * map_bytes > 32 * 1024) G >>= 1;
-  a.G = G;
+  const int G = a.G = games_per_workgroup(map_bytes);
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   hipLaunchKernelGGL(seek_kernel, dim3(grid), dim3(64 * G), (size_t)G * map_bytes,
                      (hipStream_t)stream, a);

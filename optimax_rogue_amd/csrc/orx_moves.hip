@@ -223,8 +223,7 @@ extern "C" int orx_moves(const orx_cfg_t* cfg, const orx_state_t* st, int32_t pl
   if (!kind) return fail(ORX_EINVAL, "orx_moves: kind is NULL");
   if ((r = check_games("orx_moves", n_games))) return r;
   // (a row is one vector store)
-  if ((reinterpret_cast<uintptr_t>(kind) & 7) || (reinterpret_cast<uintptr_t>(target) & 15) ||
-      (reinterpret_cast<uintptr_t>(amount) & 15))
+  if (misaligned(kind, 8) || misaligned(target, 16) || misaligned(amount, 16))
     return fail(ORX_EINVAL, "orx_moves: kind must be 8-byte, target and amount 16-byte aligned");
   if ((r = check_state(cfg, st, kPlayers | kStairsNoBank | kBank | kNpcs | kGrid | kCharacter |
                                     kItems)))

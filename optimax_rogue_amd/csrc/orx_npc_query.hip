@@ -30,19 +30,18 @@
 //     byte reads of the game's occupancy grid, and the hit slot's alive bit
 //     and health only where a target is hit (as orx_moves does).
 // The seek helpers (the closed-form room distance and the first-move rule) are
-// restated from orx_path.hip rather than lifted out of it, so that file and
-// its build id stay what they are.
+// orx_seek.h's, the ones orx_path_seek uses.
 // Plain C++ and vector stores only.
 #include "../../include/orx_npc_query.h"
 #include "orx_query.h"
+#include "orx_seek.h"
 
 namespace orx_npc_query_dev {
 
 using namespace orx_query;
 
 constexpr uint32_t kNoCell = 0xFFFFFFFFu;  // the packed key of a target outside the grid
-constexpr uint32_t kNoPath = 0x7FFFFFFFu;  // a target that cannot be reached (above every distance)
-constexpr uint32_t kAbsent = 0xFFFFFFFFu;  // no target at all (above kNoPath)
+constexpr uint32_t kAbsent = 0xFFFFFFFFu;  // no target at all (above orx_seek.h's kNoPath)
 
 // What both kernels read of a game: the players and the NPCs' depth.
 struct GameArgs {
@@ -261,52 +260,6 @@ __global__ __launch_bounds__(kBlock) void options_kernel(const OptionsArgs a) {
   store_options(a, row, kd, tg, am);
 }
 
-// One NPC's cell and the distances from it (orx_path.hip's Seeker, restated).
-struct Seeker {
-  int W, H, x, y, sx, sy;
-  const uint16_t* table;  // pairs[layout], or nullptr: the closed form
-  const uint8_t* tiles;   // bank_tiles[layout], with the table
-
-  __device__ __forceinline__ bool inside(int cx, int cy) const {
-    return (uint32_t)cx < (uint32_t)W && (uint32_t)cy < (uint32_t)H;
-  }
-  // the walking distance between cells (ax, ay) and (tx, ty), both in the
-  // grid; kNoPath where there is no walk (or a cell is Wall)
-  __device__ __forceinline__ uint32_t between(int ax, int ay, int tx, int ty) const {
-    if (table) {
-      const uint32_t v = table[(size_t)(tx * H + ty) * (size_t)(W * H) + (size_t)(ax * H + ay)];
-      return v >= (uint32_t)ORX_PATH_UNREACHABLE ? kNoPath : v;
-    }
-    // EmptyDungeonGenerator: border Wall; an open interior at least two cells
-    // wide, so only a staircase strictly between two cells of one row or
-    // column costs a detour, of two moves
-    if (ax < 1 || ax > W - 2 || ay < 1 || ay > H - 2 || tx < 1 || tx > W - 2 || ty < 1 || ty > H - 2)
-      return kNoPath;
-    const int dx = ax - tx, dy = ay - ty;
-    uint32_t d = (uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy));
-    if (dx == 0 && sx == ax && (ay < sy) != (ty < sy) && sy != ay && sy != ty) d += 2u;
-    if (dy == 0 && sy == ay && (ax < sx) != (tx < sx) && sx != ax && sx != tx) d += 2u;
-    return d;
-  }
-  __device__ __forceinline__ bool staircase(int cx, int cy) const {
-    return tiles ? (tiles[cx * H + cy] & 3u) == ORX_TILE_STAIRCASE_DOWN : (cx == sx && cy == sy);
-  }
-  // the first of Up, Right, Down, Left whose cell is at dist - 1 from the
-  // target; a staircase counts only as the target's own cell
-  __device__ __forceinline__ uint32_t move_to(uint32_t dist, int tx, int ty) const {
-    if (dist == 0u || dist >= kNoPath) return ORX_MOVE_STAY;
-    const int nx[4] = {x, x + 1, x, x - 1}, ny[4] = {y - 1, y, y + 1, y};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (!inside(nx[j], ny[j])) continue;
-      if (between(nx[j], ny[j], tx, ty) != dist - 1u) continue;
-      if (staircase(nx[j], ny[j]) && !(nx[j] == tx && ny[j] == ty)) continue;
-      return (uint32_t)(ORX_MOVE_UP + j);
-    }
-    return ORX_MOVE_STAY;
-  }
-};
-
 __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
   const GameArgs& g = a.g;
   const int64_t B = g.B;
@@ -345,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
   }
 
   const int near = reach[1] < reach[0] ? 1 : 0;  // (player 1 wins a tie)
-  uint32_t dist[4], mv[4], target[4];
+  uint32_t dist[3], mv[3], target[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     const int p = j < 2 ? j : near;
@@ -355,16 +308,12 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
     mv[j] = move[p];
     target[j] = reach[p] == kAbsent ? 0xFFFFu : (uint32_t)(p + 1);
   }
-  dist[3] = (uint32_t)ORX_SEEK_ABSENT, mv[3] = ORX_MOVE_STAY, target[3] = 0xFFFFu;
 
   // a lane's row of each output: one store
-  if (a.dist)
-    reinterpret_cast<uint4*>(a.dist)[row] = make_uint4(dist[0], dist[1], dist[2], dist[3]);
-  if (a.move)
-    reinterpret_cast<uint32_t*>(a.move)[row] = mv[0] | mv[1] << 8 | mv[2] << 16 | mv[3] << 24;
+  store_seek_rows(a.dist, a.move, row, dist[0], dist[1], dist[2], mv[0], mv[1], mv[2]);
   if (a.target)
     reinterpret_cast<uint2*>(a.target)[row] =
-        make_uint2(target[0] | target[1] << 16, target[2] | target[3] << 16);
+        make_uint2(target[0] | target[1] << 16, target[2] | 0xFFFFu << 16);
 }
 
 // the refusals both entry points share, and the game's part of the arguments
@@ -410,8 +359,7 @@ extern "C" int orx_npc_options(const orx_cfg_t* cfg, const orx_state_t* st, uint
     return r;
   if (!kind) return fail(ORX_EINVAL, "orx_npc_options: kind is NULL");
   // (a row is one vector store)
-  if ((reinterpret_cast<uintptr_t>(kind) & 7) || (reinterpret_cast<uintptr_t>(target) & 15) ||
-      (reinterpret_cast<uintptr_t>(amount) & 15))
+  if (misaligned(kind, 8) || misaligned(target, 16) || misaligned(amount, 16))
     return fail(ORX_EINVAL,
                 "orx_npc_options: kind must be 8-byte, target and amount 16-byte aligned");
   a.kind = kind, a.target = target, a.amount = amount, a.where = where;
@@ -433,8 +381,7 @@ extern "C" int orx_npc_seek(const orx_cfg_t* cfg, const orx_state_t* st, const u
   if (!st->p_depth) return fail(ORX_EINVAL, "a required state pointer is NULL");
   if (!dist && !move && !target)
     return fail(ORX_EINVAL, "orx_npc_seek: dist, move and target are all NULL");
-  if ((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(move) & 3) ||
-      (reinterpret_cast<uintptr_t>(target) & 7))
+  if (misaligned(dist, 16) || misaligned(move, 4) || misaligned(target, 8))
     return fail(ORX_EINVAL,
                 "orx_npc_seek: dist must be 16-byte, move 4-byte and target 8-byte aligned");
   if (cfg->n_layouts > 0 && !pairs) return fail(ORX_EINVAL, "orx_npc_seek: n_layouts > 0 needs pairs");

@@ -50,12 +50,14 @@
 // seek_kernel: moves_kernel's shape -- one lane per game, 256 per workgroup,
 // no LDS.  A lane reads one table cell per target (row = the target's cell,
 // column = its own: the table is symmetric), keeps the least per column, and
-// reads the chosen target's row at its four neighbours for the move.
+// reads the chosen target's row at its four neighbours for the move (the
+// Seeker of orx_seek.h, which orx_npc_seek shares).
 // Plain C++ and vector stores only.
 #include <cstdlib>
 
 #include "../../include/orx_path.h"
 #include "orx_query.h"
+#include "orx_seek.h"
 
 namespace orx_path_dev {
 
@@ -510,54 +512,6 @@ struct SeekArgs {
   int32_t W, H, K, L, player, npc_depth, items;
 };
 
-constexpr uint32_t kNoPath = 0x7FFFFFFFu;  // a target that cannot be reached (above every distance)
-
-// One game's viewer: its cell, and the distances from it.
-struct Seeker {
-  int W, H, x, y, sx, sy;
-  const uint16_t* table;  // pairs[layout], or nullptr: the closed form
-  const uint8_t* tiles;   // bank_tiles[layout], with the table
-
-  __device__ __forceinline__ bool inside(int cx, int cy) const {
-    return (uint32_t)cx < (uint32_t)W && (uint32_t)cy < (uint32_t)H;
-  }
-  // the walking distance between cells (ax, ay) and (tx, ty), both in the
-  // grid; kNoPath where there is no walk (or a cell is Wall)
-  __device__ __forceinline__ uint32_t between(int ax, int ay, int tx, int ty) const {
-    if (table) {
-      const uint32_t v = table[(size_t)(tx * H + ty) * (size_t)(W * H) + (size_t)(ax * H + ay)];
-      return v >= kFar ? kNoPath : v;
-    }
-    // EmptyDungeonGenerator: border Wall; an open interior at least two cells
-    // wide, so only a staircase strictly between two cells of one row or
-    // column costs a detour, of two moves
-    if (ax < 1 || ax > W - 2 || ay < 1 || ay > H - 2 || tx < 1 || tx > W - 2 || ty < 1 || ty > H - 2)
-      return kNoPath;
-    const int dx = ax - tx, dy = ay - ty;
-    uint32_t d = (uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy));
-    if (dx == 0 && sx == ax && (ay < sy) != (ty < sy) && sy != ay && sy != ty) d += 2u;
-    if (dy == 0 && sy == ay && (ax < sx) != (tx < sx) && sx != ax && sx != tx) d += 2u;
-    return d;
-  }
-  __device__ __forceinline__ bool staircase(int cx, int cy) const {
-    return tiles ? tiles[cx * H + cy] == ORX_TILE_STAIRCASE_DOWN : (cx == sx && cy == sy);
-  }
-  // the first of Up, Right, Down, Left whose cell is at dist - 1 from the
-  // target; a staircase counts only as the target's own cell
-  __device__ __forceinline__ int32_t move_to(uint32_t dist, int tx, int ty) const {
-    if (dist == 0u || dist == kNoPath) return ORX_MOVE_STAY;
-    const int nx[4] = {x, x + 1, x, x - 1}, ny[4] = {y - 1, y, y + 1, y};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (!inside(nx[j], ny[j])) continue;
-      if (between(nx[j], ny[j], tx, ty) != dist - 1u) continue;
-      if (staircase(nx[j], ny[j]) && !(nx[j] == tx && ny[j] == ty)) continue;
-      return ORX_MOVE_UP + j;
-    }
-    return ORX_MOVE_STAY;
-  }
-};
-
 // the least distance of a column and the lowest slot attaining it
 struct Nearest {
   uint32_t dist = kNoPath;
@@ -611,7 +565,7 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
     }
   }
 
-  uint32_t dist[4], move[4], target[4];
+  uint32_t dist[3], move[3], target[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     const Nearest& n = col[j];
@@ -620,15 +574,12 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
     move[j] = (uint32_t)(n.slot < 0 ? ORX_MOVE_STAY : s.move_to(n.dist, n.tx, n.ty));
     target[j] = (uint32_t)n.slot & 0xFFFFu;
   }
-  dist[3] = (uint32_t)ORX_SEEK_ABSENT, move[3] = ORX_MOVE_STAY, target[3] = 0xFFFFu;
 
   // a game's row of each output: one store
-  if (a.dist) reinterpret_cast<uint4*>(a.dist)[b] = make_uint4(dist[0], dist[1], dist[2], dist[3]);
-  if (a.move)
-    reinterpret_cast<uint32_t*>(a.move)[b] = move[0] | move[1] << 8 | move[2] << 16 | move[3] << 24;
+  store_seek_rows(a.dist, a.move, b, dist[0], dist[1], dist[2], move[0], move[1], move[2]);
   if (a.target)
     reinterpret_cast<uint2*>(a.target)[b] =
-        make_uint2(target[0] | target[1] << 16, target[2] | target[3] << 16);
+        make_uint2(target[0] | target[1] << 16, target[2] | 0xFFFFu << 16);
 }
 
 }  // namespace orx_path_dev
@@ -762,8 +713,7 @@ extern "C" int orx_path_seek(const orx_cfg_t* cfg, const orx_state_t* st, const 
     return fail(ORX_EINVAL, "orx_path_seek: dist, move and target are all NULL");
   if ((r = check_games("orx_path_seek", n_games))) return r;
   // (a row is one vector store)
-  if ((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(move) & 3) ||
-      (reinterpret_cast<uintptr_t>(target) & 7))
+  if (misaligned(dist, 16) || misaligned(move, 4) || misaligned(target, 8))
     return fail(ORX_EINVAL,
                 "orx_path_seek: dist must be 16-byte, move 4-byte and target 8-byte aligned");
   if ((r = check_state(cfg, st, kStairsNoBank | kBank | kNpcs | kItems))) return r;

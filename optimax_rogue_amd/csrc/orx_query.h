@@ -22,12 +22,18 @@ namespace orx_query {
 constexpr int kBlock = 256;
 constexpr int kTileBudget = 40 * 1024;  // LDS bytes of a workgroup's tiles (all planes)
 
+// 2^32 / d + 1, the reciprocal the kernels divide by: __umulhi(n, recip(d)) ==
+// n / d while n * d < 2^32, which holds for n < 2^16 and d <= 2^16.  (recip(d)
+// = (2^32 + e) / d with 0 < e <= d, so n recip(d) / 2^32 = n / d + n e / (d 2^32):
+// above n / d by less than 1 / d while n e < 2^32, too little to reach the next integer.)
+inline uint32_t recip(int d) { return (uint32_t)(0x100000000ULL / (uint64_t)d) + 1u; }
+
 // The window: V x V cells around the player, G games per workgroup.  (The
 // kernels' argument blocks keep R, G and the reciprocals where they were --
 // the layout is part of the device code -- and the kernel calls `of`.)
 struct Window {
   int32_t R, V, VV, G;
-  uint32_t inv_vv, inv_v;  // 2^32 / VV + 1 and 2^32 / V + 1: __umulhi(n, inv) = n / d for n < 2^16
+  uint32_t inv_vv, inv_v;  // recip(VV) and recip(V)
 
   __host__ __device__ __forceinline__ static Window of(int R, int G, uint32_t inv_vv,
                                                        uint32_t inv_v) {
@@ -41,8 +47,7 @@ struct Window {
     const int V = 2 * radius + 1, VV = V * V;
     int G = cap;
     while (G > 16 && G * VV * cell_bytes > kTileBudget) G >>= 1;
-    return of(radius, G, (uint32_t)(0x100000000ULL / (uint64_t)VV) + 1u,
-              (uint32_t)(0x100000000ULL / (uint64_t)V) + 1u);
+    return of(radius, G, recip(VV), recip(V));
   }
 
   __device__ __forceinline__ int div_v(uint32_t n) const { return (int)__umulhi(n, inv_v); }
@@ -55,6 +60,34 @@ struct Window {
     return {g, j, (int)r - j * V};
   }
 };
+
+// the window columns that lie in the grid's x range, as row-word bits (bit i:
+// window column i of a viewer at x = px)
+__device__ __forceinline__ uint32_t grid_columns(int px, int W, int R, int V) {
+  const int i0 = R - px, i1 = W - 1 - px + R;  // window columns of x = 0 and x = W - 1
+  const int lo = i0 > 0 ? i0 : 0, hi = i1 < V - 1 ? i1 : V - 1;
+  return lo <= hi ? ((2u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+}
+
+// bits [i, i + 16) of the window's flat cell sequence starting at row `row`,
+// column `i`, out of per-row words: the cells run over a row's end into the next
+__device__ __forceinline__ uint32_t gather16(const uint32_t* words, int row, int i, int V) {
+  uint32_t bits = 0;
+  int filled = 0;
+  while (filled < 16) {
+    const int take = V - i < 16 - filled ? V - i : 16 - filled;
+    bits |= ((words[row] >> i) & ((1u << take) - 1u)) << filled;
+    filled += take;
+    i = 0;
+    ++row;
+  }
+  return bits;
+}
+
+// bits 0..3 of n -> the low bit of bytes 0..3 (times 0xFF: all of their bits)
+__device__ __forceinline__ uint32_t spread4(uint32_t n) {
+  return ((n & 15u) * 0x00204081u) & 0x01010101u;
+}
 
 // tile[0 .. n) (LDS, 16-byte aligned) -> out[0 .. n): 16 bytes per lane while
 // out is 16-byte aligned, the rest (all of it, if out is not) element by element
@@ -95,6 +128,8 @@ inline bool has_items(const orx_cfg_t* cfg) {
 }
 
 // The entry points' shared refusals (`fn`: the entry point's name).
+// p is not a multiple of n, a power of two (a NULL pointer is aligned)
+inline bool misaligned(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) & (n - 1); }
 inline int fail_in(const char* fn, const char* msg) {
   char buf[128];
   snprintf(buf, sizeof(buf), "%s: %s", fn, msg);

@@ -36,10 +36,13 @@
 // keeps the compiler from reordering them.  There is no workgroup barrier in
 // the kernel, so waves of one workgroup whose searches differ in length never
 // wait for each other.  Every loop is bounded by the step count (<= W * H) and
-// ends at a step that reaches nothing new.  Plain C++ and vector stores only;
+// ends at a step that reaches nothing new.  The key's rule, the wave's
+// reductions, the dist / move stores and the host side's refusals are
+// orx_seek.h's, shared with orx_explore.hip; frontier_bits is there too.  Plain C++ and vector stores only;
 // no atomics; each output row is one store from lane 0.
 #include "../../include/orx_route.h"
 #include "orx_query.h"
+#include "orx_seek.h"
 
 namespace orx_route_dev {
 
@@ -47,29 +50,6 @@ using namespace orx_query;
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // no cell (above every flat cell)
 constexpr int kStagedPlanes = 5, kBarePlanes = 2;
-
-// whether key row k is valid for a state (orx_explore.h's rule, restated)
-__device__ __forceinline__ bool key_valid(const int4 k, int32_t episode, int32_t depth,
-                                          int32_t tick) {
-  return k.w >= 0 && k.x == episode && k.y == depth && k.z <= tick;
-}
-
-// the least of a word over the wave (orx_explore.hip's, restated)
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
-// the wave's LDS stores so far are visible to its loads from here on
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(kBlock) void planes_kernel(const uint8_t* tiles, uint32_t* planes,
                                                         int64_t n_words, int W, int H, int WW) {
@@ -102,7 +82,7 @@ struct RouteArgs {
   int32_t* target;
   int64_t B;
   int32_t W, H, WW, L, player, G;
-  uint32_t inv_ww, inv_h;  // 2^32 / d + 1: __umulhi(n, inv) = n / d for n < 2^16 (WW > 1)
+  uint32_t inv_ww, inv_h;  // recip(WW), recip(H): __umulhi(n, inv) = n / d for n < 2^16 (WW > 1)
 };
 
 // What the search needs of one map word: the known cells that are Ground, those
@@ -137,13 +117,8 @@ struct Map {
       g &= ~s;
     }
     r.pass = k & g, r.stairs = k & s;
-    if (want_front && r.pass) {
-      // a cell off the grid counts as known (it is no one's frontier)
-      const uint32_t up = y > 0 ? known[i - WW] : ~0u, down = y < H - 1 ? known[i + WW] : ~0u;
-      const uint32_t left = k << 1 | (xw > 0 ? known[i - 1] >> 31 : 1u);
-      const uint32_t right = k >> 1 | (xw < last_word ? known[i + 1] << 31 : last_bit);
-      r.front = r.pass & ~(up & down & left & right);
-    }
+    if (want_front && r.pass)
+      r.front = r.pass & frontier_bits(known, k, i, y, xw, WW, H, last_word, last_bit);
     return r;
   }
 };
@@ -330,12 +305,8 @@ __global__ __launch_bounds__(kBlock) void route_kernel(const RouteArgs a) {
     const uint32_t nib = (steps >> (4 * col)) & 15u;
     mv[col] = nib ? (uint32_t)(ORX_MOVE_UP + __builtin_ctz(nib)) : (uint32_t)ORX_MOVE_STAY;
   }
-  const uint32_t absent = (uint32_t)ORX_SEEK_ABSENT, stay = ORX_MOVE_STAY;
-  if (a.dist)
-    reinterpret_cast<uint4*>(a.dist)[b] =
-        make_uint4((uint32_t)found[0], (uint32_t)found[1], (uint32_t)found[2], absent);
-  if (a.move)
-    reinterpret_cast<uint32_t*>(a.move)[b] = mv[0] | mv[1] << 8 | mv[2] << 16 | stay << 24;
+  store_seek_rows(a.dist, a.move, b, (uint32_t)found[0], (uint32_t)found[1], (uint32_t)found[2],
+                  mv[0], mv[1], mv[2]);
   if (a.target) reinterpret_cast<uint4*>(a.target)[b] = make_uint4(cell[0], cell[1], cell[2], kNone);
 }
 
@@ -346,10 +317,6 @@ __global__ __launch_bounds__(kBlock) void route_kernel(const RouteArgs a) {
 #endif
 
 extern "C" const char* orx_route_build_id(void) { return ORX_ROUTE_BUILD_ID; }
-
-namespace {
-inline bool misaligned(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) & (n - 1); }
-}  // namespace
 
 extern "C" int orx_route_planes(const orx_cfg_t* cfg, const uint8_t* bank_tiles, uint32_t* planes,
                                 void* stream) {
@@ -376,22 +343,10 @@ extern "C" int orx_route(const orx_cfg_t* cfg, const orx_state_t* st, const uint
   using orx_dev::fail;
   int r;
   if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_route", player))) return r;
-  if (!memory || !key) return fail(ORX_EINVAL, "orx_route: memory or key is NULL");
-  if (misaligned(memory, 4) || misaligned(key, 16))
-    return fail(ORX_EINVAL, "orx_route: memory must be 4-byte and key 16-byte aligned");
-  if (!dist && !move && !target)
-    return fail(ORX_EINVAL, "orx_route: dist, move and target are all NULL");
-  // (a row is one vector store)
-  if (misaligned(dist, 16) || misaligned(move, 4) || misaligned(target, 16))
-    return fail(ORX_EINVAL, "orx_route: dist and target must be 16-byte and move 4-byte aligned");
+  if ((r = check_memory_rows("orx_route", memory, key, dist, move, target))) return r;
   if (misaligned(goal, 4) || misaligned(planes, 4))
     return fail(ORX_EINVAL, "orx_route: goal and planes must be 4-byte aligned");
-  if ((r = check_games("orx_route", n_games))) return r;
-  if ((int64_t)cfg->width * cfg->height > 65536)
-    return fail(ORX_EINVAL, "orx_route: a flat cell must fit 16 bits (W * H <= 65536)");
-  if ((r = check_state(cfg, st, kStairsNoBank | kBank))) return r;
-  if (!st->p_depth || !st->tick || !st->episode)
-    return fail(ORX_EINVAL, "a required state pointer is NULL");
+  if ((r = check_memory_query("orx_route", cfg, st, n_games))) return r;
   if (cfg->n_layouts > 0 && !planes) return fail(ORX_EINVAL, "orx_route: n_layouts > 0 needs planes");
 
   RouteArgs a;
@@ -404,17 +359,15 @@ extern "C" int orx_route(const orx_cfg_t* cfg, const orx_state_t* st, const uint
   a.B = n_games;
   a.W = cfg->width, a.H = cfg->height, a.WW = (cfg->width + 31) / 32, a.L = cfg->n_layouts;
   a.player = player;
-  a.inv_ww = (uint32_t)(0x100000000ULL / (uint64_t)(a.WW > 1 ? a.WW : 2)) + 1u;
-  a.inv_h = (uint32_t)(0x100000000ULL / (uint64_t)cfg->height) + 1u;
+  a.inv_ww = recip(a.WW > 1 ? a.WW : 2);
+  a.inv_h = recip(cfg->height);
   // a wave per game.  Five planes a game while they fit 64 KiB, four games to
   // a workgroup while theirs fit 32 KiB; else the two reached planes alone
   // (W * H <= 65536 and W >= 4: one plane is at most 64 KiB, two fit the CU's LDS)
   const size_t plane_bytes = sizeof(uint32_t) * (size_t)a.H * (size_t)a.WW;
   const bool staged = kStagedPlanes * plane_bytes <= 64 * 1024;
   const size_t game_bytes = (staged ? kStagedPlanes : kBarePlanes) * plane_bytes;
-  int G = 4;
-  while (G > 1 && (size_t)G * game_bytes > 32 * 1024) G >>= 1;
-  a.G = G;
+  const int G = a.G = games_per_workgroup(game_bytes);
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   const size_t lds = (size_t)G * game_bytes;
   if (staged) {

@@ -58,11 +58,6 @@ struct SightArgs {
   uint32_t inv_vv, inv_v;  // (R, G, inv_vv, inv_v: a Window)
 };
 
-// bits 0..3 of n -> the low bit of bytes 0..3
-__device__ __forceinline__ uint32_t spread4(uint32_t n) {
-  return ((n & 15u) * 0x00204081u) & 0x01010101u;
-}
-
 // four cells of a plane under four seen bits: seen -> code | flag, unseen -> 0
 __device__ __forceinline__ uint32_t mask4(uint32_t w, uint32_t bits, uint32_t flag) {
   const uint32_t s = spread4(bits);
@@ -79,15 +74,7 @@ __device__ __forceinline__ void mask_plane(const uint32_t* seen, uint8_t* plane,
   for (int v = t; v < nvec; v += kBlock) {
     // the 16 cells run over the end of a window row into the next rows
     const Window::Cell first = win.split((uint32_t)v << 4);
-    int row = first.g * V + first.j, i = first.i, filled = 0;
-    uint32_t bits = 0;
-    while (filled < 16) {
-      const int take = V - i < 16 - filled ? V - i : 16 - filled;
-      bits |= ((seen[row] >> i) & ((1u << take) - 1u)) << filled;
-      filled += take;
-      i = 0;
-      ++row;
-    }
+    const uint32_t bits = gather16(seen, first.g * V + first.j, first.i, V);
     uint4 w = q[v];
     w.x = mask4(w.x, bits, flag);
     w.y = mask4(w.y, bits >> 4, flag);
@@ -100,14 +87,6 @@ __device__ __forceinline__ void mask_plane(const uint32_t* seen, uint8_t* plane,
     const bool on = (seen[at.g * V + at.j] >> at.i) & 1u;
     plane[c] = on ? (uint8_t)(plane[c] | flag) : (uint8_t)0;
   }
-}
-
-// the window columns of row mask bits that lie in the grid's x range
-__device__ __forceinline__ uint32_t grid_columns(int px, int W, int R, int V) {
-  // window columns i0 and i1 are x = 0 and x = W - 1
-  const int i0 = R - px, i1 = W - 1 - px + R;
-  const int lo = i0 > 0 ? i0 : 0, hi = i1 < V - 1 ? i1 : V - 1;
-  return lo <= hi ? ((2u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
 }
 
 __global__ __launch_bounds__(kBlock) void sight_kernel(const SightArgs a) {
@@ -277,7 +256,7 @@ extern "C" int orx_sight(const orx_cfg_t* cfg, const orx_state_t* st, int32_t pl
     return fail(ORX_EINVAL, "orx_sight: radius must be in [1, ORX_VIEW_MAX_RADIUS]");
   if (!rows && !cells && !health)
     return fail(ORX_EINVAL, "orx_sight: rows, cells and health are all NULL");
-  if (reinterpret_cast<uintptr_t>(rows) & 3)
+  if (misaligned(rows, 4))
     return fail(ORX_EINVAL, "orx_sight: rows must be 4-byte aligned");
   if ((r = check_games("orx_sight", n_games)) || (r = check_state(cfg, st, kBank))) return r;
 
@@ -288,11 +267,10 @@ extern "C" int orx_sight(const orx_cfg_t* cfg, const orx_state_t* st, int32_t pl
   a.B = n_games;
   a.W = cfg->width, a.H = cfg->height, a.L = cfg->n_layouts;
   a.player = player;
-  const int G = kGames, V = 2 * radius + 1, VV = V * V;
-  a.R = radius, a.G = G;
-  a.inv_vv = (uint32_t)(0x100000000ULL / (uint64_t)VV) + 1u;
-  a.inv_v = (uint32_t)(0x100000000ULL / (uint64_t)V) + 1u;
-  const size_t lds = sizeof(uint32_t) * (size_t)G * (size_t)(3 * V + kHdr);
+  const Window win = Window::fit(radius, 0, kGames);  // (no tiles: always kGames games)
+  const int G = win.G;
+  a.R = win.R, a.G = G, a.inv_vv = win.inv_vv, a.inv_v = win.inv_v;
+  const size_t lds = sizeof(uint32_t) * (size_t)G * (size_t)(3 * win.V + kHdr);
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   hipLaunchKernelGGL(sight_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, a);
   return orx_dev::launch_status("orx_sight");

@@ -71,11 +71,6 @@ __device__ __forceinline__ uint32_t clamp_u8(int32_t v) {
   return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
 
-// bits 0..3 of n -> the low bit of bytes 0..3
-__device__ __forceinline__ uint32_t spread4(uint32_t n) {
-  return ((n & 15u) * 0x00204081u) & 0x01010101u;
-}
-
 // NPC slots k0 .. k0 + kChunk of the workgroup's games -> stage, one lane per
 // (slot, game): coalesced over the games
 __device__ __forceinline__ void stage_npcs(const ViewArgs& a, uint32_t* stage, int k0, int64_t b0,

@@ -318,8 +318,8 @@ def test_header_is_the_export_table():
 
 def test_explore_symbols_and_build_id(engine_lib):
     """The library exports the header's entry points; its explore id is the
-    hash of orx_explore.hip, orx_explore.h and orx_query.h and shows only under
-    ``every=True``."""
+    hash of orx_explore.hip, orx_explore.h, orx_query.h and orx_seek.h and
+    shows only under ``every=True``."""
     from optimax_rogue_amd import _lib, build
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
                          text=True, check=True).stdout
@@ -330,12 +330,12 @@ def test_explore_symbols_and_build_id(engine_lib):
     hdr = os.path.join(ROOT, "include", "orx_explore.h")
     assert (src, hdr) == (build.EXPLORE_SRC, build.EXPLORE_HDR)
     h = hashlib.sha256()
-    for p in (src, hdr, build.QUERY_HDR):
+    for p in (src, hdr, build.QUERY_HDR, build.SEEK_HDR):
         with open(p, "rb") as f:
             h.update(f.read())
     assert build.explore_id() == h.hexdigest()[:16] == _lib.explore_build_id()
     assert build.PARTS["explore"] == build.Part("orx_explore_build_id", "ORX_EXPLORE_BUILD_ID",
-                                                (src, hdr, build.QUERY_HDR), ())
+                                                (src, hdr, build.QUERY_HDR, build.SEEK_HDR), ())
     assert src in build.EXTRA_SOURCES and src in build.SOURCES
     ids = build.built_ids(_lib.LIB_PATH, every=True)
     assert ids == build.tree_ids() and ids["explore"] == build.explore_id()

@@ -224,8 +224,9 @@ def test_header_is_the_export_table():
 
 def test_npc_query_symbols_and_build_id(engine_lib):
     """The library exports the header's entry points; its npc_query id is the
-    hash of orx_npc_query.hip, orx_npc_query.h and orx_query.h and shows only
-    under ``every=True``; the other parts name the files they always named."""
+    hash of orx_npc_query.hip, orx_npc_query.h, orx_query.h and orx_seek.h and
+    shows only under ``every=True``; the parts that were there name their own
+    files (path with orx_seek.h, which it shares)."""
     from optimax_rogue_amd import _lib, build
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
                          text=True, check=True).stdout
@@ -241,10 +242,11 @@ def test_npc_query_symbols_and_build_id(engine_lib):
         return h.hexdigest()[:16]
     src = os.path.join(ROOT, "optimax_rogue_amd", "csrc", "orx_npc_query.hip")
     hdr = os.path.join(ROOT, "include", "orx_npc_query.h")
-    assert build.npc_query_id() == digest((src, hdr, build.QUERY_HDR)) == _lib.npc_query_build_id()
+    files = (src, hdr, build.QUERY_HDR, build.SEEK_HDR)
+    assert build.npc_query_id() == digest(files) == _lib.npc_query_build_id()
     part = build.PARTS["npc_query"]
     assert part.symbol == "orx_npc_query_build_id" and part.macro == "ORX_NPC_QUERY_BUILD_ID"
-    assert part.files == (src, hdr, build.QUERY_HDR) and part.sources == ()
+    assert part.files == files and part.sources == ()
     assert src in build.SOURCES and build.SOURCES[0] == build.SRC
     ids = build.built_ids(_lib.LIB_PATH, every=True)
     assert ids == build.tree_ids() and ids["npc_query"] == build.npc_query_id()
@@ -252,7 +254,8 @@ def test_npc_query_symbols_and_build_id(engine_lib):
     # the files of the parts that were there are the files they were
     assert build.PARTS["engine"].files == (build.SRC, build.HDR, build.VIEW_SRC, build.VIEW_HDR,
                                            build.QUERY_HDR, build.PLAN_HDR)
-    assert build.PARTS["path"].files == (build.PATH_SRC, build.PATH_HDR, build.QUERY_HDR)
+    assert build.PARTS["path"].files == (build.PATH_SRC, build.PATH_HDR, build.QUERY_HDR,
+                                         build.SEEK_HDR)
     assert build.PARTS["moves"].files == (build.MOVES_SRC, build.MOVES_HDR, build.QUERY_HDR)
     assert build.PARTS["npc"].files == (build.NPC_HDR, build.SRC)
 

@@ -204,7 +204,7 @@ def test_header_constants_are_the_modules():
 
 def test_path_symbols_and_build_id(engine_lib):
     """The library exports the header's entry points, and its path id is the
-    hash of the tree's orx_path.hip, orx_path.h and the queries' shared header
+    hash of the tree's orx_path.hip, orx_path.h and the queries' shared headers
     (a stale library is rebuilt: build.build compares all ids)."""
     import hashlib
     import subprocess
@@ -215,7 +215,7 @@ def test_path_symbols_and_build_id(engine_lib):
     for name in _lib.PATH_EXPORTS:
         assert hasattr(engine_lib, name)
     h = hashlib.sha256()
-    for p in (build.PATH_SRC, build.PATH_HDR, build.QUERY_HDR):
+    for p in (build.PATH_SRC, build.PATH_HDR, build.QUERY_HDR, build.SEEK_HDR):
         with open(p, "rb") as f:
             h.update(f.read())
     assert build.path_id() == h.hexdigest()[:16] == _lib.path_build_id()

@@ -445,7 +445,7 @@ def test_header_is_the_export_table():
 
 def test_route_symbols_and_build_id(engine_lib):
     """The library exports the header's entry points; its route id is the hash
-    of orx_route.hip, orx_route.h and orx_query.h and shows only under
+    of orx_route.hip, orx_route.h, orx_query.h and orx_seek.h and shows only under
     ``every=True``."""
     from optimax_rogue_amd import _lib, build
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
@@ -457,12 +457,12 @@ def test_route_symbols_and_build_id(engine_lib):
     hdr = os.path.join(ROOT, "include", "orx_route.h")
     assert (src, hdr) == (build.ROUTE_SRC, build.ROUTE_HDR)
     h = hashlib.sha256()
-    for p in (src, hdr, build.QUERY_HDR):
+    for p in (src, hdr, build.QUERY_HDR, build.SEEK_HDR):
         with open(p, "rb") as f:
             h.update(f.read())
     assert build.route_id() == h.hexdigest()[:16] == _lib.route_build_id()
     assert build.PARTS["route"] == build.Part("orx_route_build_id", "ORX_ROUTE_BUILD_ID",
-                                              (src, hdr, build.QUERY_HDR), ())
+                                              (src, hdr, build.QUERY_HDR, build.SEEK_HDR), ())
     assert src in build.EXTRA_SOURCES and src in build.SOURCES
     ids = build.built_ids(_lib.LIB_PATH, every=True)
     assert ids == build.tree_ids() and ids["route"] == build.route_id()
