@@ -56,8 +56,9 @@ vp, i64, i32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_ui
 _int, _str = ctypes.c_int, ctypes.c_char_p
 _cfg, _st = ctypes.POINTER(OrxCfg), ctypes.POINTER(OrxState)
 
-# name -> (restype, argtypes), one table per header.  include/orx.h: what
-# every library has ...
+# header -> name -> (restype, argtypes).  include/orx.h: what every library
+# has, then what is bound only when present (an A/B diagnostic may load an
+# older build); the other headers' symbols are optional too.
 _REQUIRED = {
     "orx_abi_version": (_int, []),
     "orx_last_error": (_str, []),
@@ -73,75 +74,67 @@ _REQUIRED = {
     "orx_build_id": (_str, []),
     "orx_rollout_lanes": (_int, [i64]),
 }
-# ... and what is bound only when present (an A/B diagnostic may load an older build)
-_OPTIONAL = {
-    "orx_dstore_depths": (_int, [_cfg]),
-    "orx_rollout_shape": (_int, [_cfg, i32, i32, i64, i32, i32, ctypes.POINTER(OrxRolloutShape)]),
-    "orx_rollout_concurrent": (_int, [_cfg, _st, i32, i32, i32, vp, vp, i64, u64, i64, i32, vp]),
-    "orx_env_step": (_int, [_cfg, _st, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, u64, i64, vp]),
-    "orx_rollout_ex": (_int, [_cfg, _st, i32, i32, i32, vp, vp, i32, i64, u64, i64, i32, vp]),
-    "orx_env_step_ex": (_int, [_cfg, _st, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, u64, i64,
-                               vp]),
-    "orx_step_n": (_int, [_cfg, _st, vp, i32, vp, i32, i64, u64, i64, vp]),
-    "orx_max_events": (_int, [_cfg]),
-    "orx_step_n_ex": (_int, [_cfg, _st, vp, i32, vp, i32, i64, u64, i64, i32, vp]),
-    "orx_env_step_args": (_int, [ctypes.POINTER(OrxEnvStepArgs)]),
+TABLES = {
+    "orx.h": {
+        **_REQUIRED,
+        "orx_dstore_depths": (_int, [_cfg]),
+        "orx_rollout_shape": (_int, [_cfg, i32, i32, i64, i32, i32,
+                                     ctypes.POINTER(OrxRolloutShape)]),
+        "orx_rollout_concurrent": (_int, [_cfg, _st, i32, i32, i32, vp, vp, i64, u64, i64, i32,
+                                          vp]),
+        "orx_env_step": (_int, [_cfg, _st, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, u64, i64,
+                                vp]),
+        "orx_rollout_ex": (_int, [_cfg, _st, i32, i32, i32, vp, vp, i32, i64, u64, i64, i32, vp]),
+        "orx_env_step_ex": (_int, [_cfg, _st, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, u64,
+                                   i64, vp]),
+        "orx_step_n": (_int, [_cfg, _st, vp, i32, vp, i32, i64, u64, i64, vp]),
+        "orx_max_events": (_int, [_cfg]),
+        "orx_step_n_ex": (_int, [_cfg, _st, vp, i32, vp, i32, i64, u64, i64, i32, vp]),
+        "orx_env_step_args": (_int, [ctypes.POINTER(OrxEnvStepArgs)]),
+    },
+    "orx_view.h": {"orx_view": (_int, [_cfg, _st, i32, i32, vp, vp, i64, vp])},
+    "orx_path.h": {
+        "orx_path_field": (_int, [_cfg, vp, vp, vp]),
+        "orx_path_query": (_int, [_cfg, _st, vp, i32, i32, vp, vp, vp, i64, vp]),
+        "orx_path_build_id": (_str, []),
+        "orx_path_rows": (_int, [_cfg, vp, vp, vp, vp, i64, vp]),
+        "orx_path_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, i64, vp]),
+    },
+    "orx_moves.h": {
+        "orx_moves": (_int, [_cfg, _st, i32, vp, vp, vp, i64, vp]),
+        "orx_moves_build_id": (_str, []),
+    },
+    "orx_npc.h": {
+        "orx_npc_max_events": (_int, [_cfg]),
+        "orx_npc_step": (_int, [_cfg, _st, vp, vp, i64, u64, i64, vp]),
+        "orx_npc_step_events": (_int, [_cfg, _st, vp, vp, vp, vp, i64, u64, i64, vp]),
+        "orx_npc_step_n": (_int, [_cfg, _st, vp, vp, i32, vp, i32, i64, u64, i64, i32, vp]),
+        "orx_npc_env_step": (_int, [ctypes.POINTER(OrxEnvStepArgs), vp]),
+        "orx_npc_build_id": (_str, []),
+    },
+    "orx_npc_query.h": {
+        "orx_npc_options": (_int, [_cfg, _st, vp, vp, vp, vp, i64, vp]),
+        "orx_npc_seek": (_int, [_cfg, _st, vp, vp, vp, vp, i64, vp]),
+        "orx_npc_query_build_id": (_str, []),
+    },
+    "orx_sight.h": {
+        "orx_sight": (_int, [_cfg, _st, i32, i32, vp, vp, vp, i64, vp]),
+        "orx_sight_build_id": (_str, []),
+    },
+    "orx_explore.h": {
+        "orx_explore_update": (_int, [_cfg, _st, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "orx_explore_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, vp, vp, i64, vp]),
+        "orx_explore_build_id": (_str, []),
+    },
+    "orx_route.h": {
+        "orx_route_planes": (_int, [_cfg, vp, vp, vp]),
+        "orx_route": (_int, [_cfg, _st, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "orx_route_build_id": (_str, []),
+    },
 }
-# include/orx_view.h, orx_path.h, orx_moves.h, orx_npc.h, orx_npc_query.h (EXPORTS is orx.h
-# alone); optional too
-_VIEW = {"orx_view": (_int, [_cfg, _st, i32, i32, vp, vp, i64, vp])}
-_PATH = {
-    "orx_path_field": (_int, [_cfg, vp, vp, vp]),
-    "orx_path_query": (_int, [_cfg, _st, vp, i32, i32, vp, vp, vp, i64, vp]),
-    "orx_path_build_id": (_str, []),
-    "orx_path_rows": (_int, [_cfg, vp, vp, vp, vp, i64, vp]),
-    "orx_path_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, i64, vp]),
-}
-_MOVES = {
-    "orx_moves": (_int, [_cfg, _st, i32, vp, vp, vp, i64, vp]),
-    "orx_moves_build_id": (_str, []),
-}
-_NPC = {
-    "orx_npc_max_events": (_int, [_cfg]),
-    "orx_npc_step": (_int, [_cfg, _st, vp, vp, i64, u64, i64, vp]),
-    "orx_npc_step_events": (_int, [_cfg, _st, vp, vp, vp, vp, i64, u64, i64, vp]),
-    "orx_npc_step_n": (_int, [_cfg, _st, vp, vp, i32, vp, i32, i64, u64, i64, i32, vp]),
-    "orx_npc_env_step": (_int, [ctypes.POINTER(OrxEnvStepArgs), vp]),
-    "orx_npc_build_id": (_str, []),
-}
-# include/orx_npc_query.h
-_NPC_QUERY = {
-    "orx_npc_options": (_int, [_cfg, _st, vp, vp, vp, vp, i64, vp]),
-    "orx_npc_seek": (_int, [_cfg, _st, vp, vp, vp, vp, i64, vp]),
-    "orx_npc_query_build_id": (_str, []),
-}
-# include/orx_sight.h
-_SIGHT = {
-    "orx_sight": (_int, [_cfg, _st, i32, i32, vp, vp, vp, i64, vp]),
-    "orx_sight_build_id": (_str, []),
-}
-# include/orx_explore.h
-_EXPLORE = {
-    "orx_explore_update": (_int, [_cfg, _st, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
-    "orx_explore_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, vp, vp, i64, vp]),
-    "orx_explore_build_id": (_str, []),
-}
-# include/orx_route.h
-_ROUTE = {
-    "orx_route_planes": (_int, [_cfg, vp, vp, vp]),
-    "orx_route": (_int, [_cfg, _st, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
-    "orx_route_build_id": (_str, []),
-}
-
-EXPORTS = tuple(_REQUIRED) + tuple(_OPTIONAL)
-VIEW_EXPORTS = tuple(_VIEW)
-PATH_EXPORTS = tuple(_PATH)
-MOVES_EXPORTS = tuple(_MOVES)
-NPC_EXPORTS = tuple(_NPC)
-NPC_QUERY_EXPORTS = tuple(_NPC_QUERY)
-SIGHT_EXPORTS = tuple(_SIGHT)
-EXPLORE_EXPORTS = tuple(_EXPLORE)
-ROUTE_EXPORTS = tuple(_ROUTE)
+EXPORTS = tuple(TABLES["orx.h"])
+(VIEW_EXPORTS, PATH_EXPORTS, MOVES_EXPORTS, NPC_EXPORTS, NPC_QUERY_EXPORTS, SIGHT_EXPORTS,
+ EXPLORE_EXPORTS, ROUTE_EXPORTS) = (tuple(t) for h, t in TABLES.items() if h != "orx.h")
 
 
 def load() -> ctypes.CDLL:
@@ -155,10 +148,9 @@ def load() -> ctypes.CDLL:
         raise RuntimeError(f"HIP engine library missing: {LIB_PATH} -- run "
                            "`python -m optimax_rogue_amd.build` first")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (_REQUIRED, _OPTIONAL, _VIEW, _PATH, _MOVES, _NPC, _NPC_QUERY, _SIGHT,
-                  _EXPLORE, _ROUTE):
+    for table in TABLES.values():
         for name, (restype, argtypes) in table.items():
-            if table is _REQUIRED or hasattr(L, name):   # (a missing required symbol raises)
+            if name in _REQUIRED or hasattr(L, name):   # (a missing required symbol raises)
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
     v = L.orx_abi_version()
@@ -179,50 +171,9 @@ def build_id() -> str:
     return load().orx_build_id().decode()
 
 
-def path_build_id() -> str:
-    """orx_path_build_id() of the loaded library (build.path_id() of its
-    sources; "" for a library built before include/orx_path.h)."""
-    L = load()
-    return L.orx_path_build_id().decode() if hasattr(L, "orx_path_build_id") else ""
-
-
-def moves_build_id() -> str:
-    """orx_moves_build_id() of the loaded library (build.moves_id() of its
-    sources; "" for a library built before include/orx_moves.h)."""
-    L = load()
-    return L.orx_moves_build_id().decode() if hasattr(L, "orx_moves_build_id") else ""
-
-
-def npc_build_id() -> str:
-    """orx_npc_build_id() of the loaded library (build.npc_id() of its sources;
-    "" for a library built before include/orx_npc.h)."""
-    L = load()
-    return L.orx_npc_build_id().decode() if hasattr(L, "orx_npc_build_id") else ""
-
-
-def npc_query_build_id() -> str:
-    """orx_npc_query_build_id() of the loaded library (build.npc_query_id() of
-    its sources; "" for a library built before include/orx_npc_query.h)."""
-    L = load()
-    return L.orx_npc_query_build_id().decode() if hasattr(L, "orx_npc_query_build_id") else ""
-
-
-def sight_build_id() -> str:
-    """orx_sight_build_id() of the loaded library (build.sight_id() of its
-    sources; "" for a library built before include/orx_sight.h)."""
-    L = load()
-    return L.orx_sight_build_id().decode() if hasattr(L, "orx_sight_build_id") else ""
-
-
-def explore_build_id() -> str:
-    """orx_explore_build_id() of the loaded library (build.explore_id() of its
-    sources; "" for a library built before include/orx_explore.h)."""
-    L = load()
-    return L.orx_explore_build_id().decode() if hasattr(L, "orx_explore_build_id") else ""
-
-
-def route_build_id() -> str:
-    """orx_route_build_id() of the loaded library (build.route_id() of its
-    sources; "" for a library built before include/orx_route.h)."""
-    L = load()
-    return L.orx_route_build_id().decode() if hasattr(L, "orx_route_build_id") else ""
+def part_id(name: str) -> str:
+    """The id of part ``name`` (build.PARTS) in the loaded library, which is
+    build.tree_ids()[name] of its sources; "" for a library built without it."""
+    from .build import PARTS
+    fn = getattr(load(), PARTS[name].symbol, None)
+    return fn().decode() if fn is not None else ""

@@ -86,25 +86,18 @@ PARTS = {
                                                                SEEK_HDR), (PATH_SRC,)),
     "moves": Part("orx_moves_build_id", "ORX_MOVES_BUILD_ID", (MOVES_SRC, MOVES_HDR, QUERY_HDR),
                   (MOVES_SRC,)),
-    "npc": Part("orx_npc_build_id", "ORX_NPC_BUILD_ID", (NPC_HDR, SRC), ()),
-    # (no `sources`: like "npc" it is read only with built_ids(every=True), so the
-    # parts a caller sees without it stay engine, path and moves; its object is
-    # named in EXTRA_SOURCES)
+    "npc": Part("orx_npc_build_id", "ORX_NPC_BUILD_ID", (NPC_HDR, SRC), ()),   # (in SRC)
     "npc_query": Part("orx_npc_query_build_id", "ORX_NPC_QUERY_BUILD_ID",
-                      (NPC_QUERY_SRC, NPC_QUERY_HDR, QUERY_HDR, SEEK_HDR), ()),
-    # (the same: its object is named in EXTRA_SOURCES)
+                      (NPC_QUERY_SRC, NPC_QUERY_HDR, QUERY_HDR, SEEK_HDR), (NPC_QUERY_SRC,)),
     "sight": Part("orx_sight_build_id", "ORX_SIGHT_BUILD_ID", (SIGHT_SRC, SIGHT_HDR, QUERY_HDR),
-                  ()),
-    # (the same)
+                  (SIGHT_SRC,)),
     "explore": Part("orx_explore_build_id", "ORX_EXPLORE_BUILD_ID",
-                    (EXPLORE_SRC, EXPLORE_HDR, QUERY_HDR, SEEK_HDR), ()),
-    # (the same)
+                    (EXPLORE_SRC, EXPLORE_HDR, QUERY_HDR, SEEK_HDR), (EXPLORE_SRC,)),
     "route": Part("orx_route_build_id", "ORX_ROUTE_BUILD_ID", (ROUTE_SRC, ROUTE_HDR, QUERY_HDR,
-                                                                  SEEK_HDR), ()),
+                                                                  SEEK_HDR), (ROUTE_SRC,)),
 }
-EXTRA_SOURCES = [NPC_QUERY_SRC, SIGHT_SRC, EXPLORE_SRC, ROUTE_SRC]
 # (SRC first: _build_parts splits it)
-SOURCES = [src for p in PARTS.values() for src in p.sources] + EXTRA_SOURCES
+SOURCES = [src for p in PARTS.values() for src in p.sources]
 
 
 def hipcc() -> str:
@@ -130,65 +123,26 @@ def source_id(defines: Iterable[str] = ()) -> str:
     return tree_ids(defines)["engine"]
 
 
-def path_id() -> str:
-    """What orx_path_build_id() of a library built from these sources returns."""
-    return tree_ids()["path"]
-
-
-def moves_id() -> str:
-    """What orx_moves_build_id() of a library built from these sources returns."""
-    return tree_ids()["moves"]
-
-
-def npc_id() -> str:
-    """What orx_npc_build_id() of a library built from these sources returns."""
-    return tree_ids()["npc"]
-
-
-def npc_query_id() -> str:
-    """What orx_npc_query_build_id() of a library built from these sources returns."""
-    return tree_ids()["npc_query"]
-
-
-def sight_id() -> str:
-    """What orx_sight_build_id() of a library built from these sources returns."""
-    return tree_ids()["sight"]
-
-
-def explore_id() -> str:
-    """What orx_explore_build_id() of a library built from these sources returns."""
-    return tree_ids()["explore"]
-
-
-def route_id() -> str:
-    """What orx_route_build_id() of a library built from these sources returns."""
-    return tree_ids()["route"]
-
-
-def built_ids(path: str = OUT, every: bool = False):
+def built_ids(path: str = OUT):
     """``tree_ids``'s dict for the library at `path` ("" for a part it was built
     without; None if it cannot be loaded), read in one child process so this
-    one does not map a library that a later build replaces.  The parts
-    compiled from sources of their own; with ``every`` also those defined in
-    another part's source ("npc", whose id follows its header too) or in
-    EXTRA_SOURCES ("npc_query", "sight", "explore", "route")."""
-    parts = {name: p for name, p in PARTS.items() if every or p.sources}
+    one does not map a library that a later build replaces."""
     code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1])\n"
             "for f in (getattr(L,s,None) for s in sys.argv[2:]):\n"
             "    f and setattr(f,'restype',ctypes.c_char_p); print(f().decode() if f else '')")
-    cmd = [sys.executable, "-c", code, path] + [p.symbol for p in parts.values()]
+    cmd = [sys.executable, "-c", code, path] + [p.symbol for p in PARTS.values()]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=60)
     except (OSError, subprocess.SubprocessError):
         return None
     lines = out.stdout.split("\n")
-    if out.returncode != 0 or len(lines) <= len(parts):
+    if out.returncode != 0 or len(lines) <= len(PARTS):
         return None
-    return {name: line.strip() for name, line in zip(parts, lines)}
+    return {name: line.strip() for name, line in zip(PARTS, lines)}
 
 
 def _fresh(out: str, ids: dict) -> bool:
-    return os.path.exists(out) and built_ids(out, every=True) == ids
+    return os.path.exists(out) and built_ids(out) == ids
 
 
 def build(force: bool = False, verbose: bool = False, defines: Iterable[str] = (),

@@ -24,10 +24,8 @@ from __future__ import annotations
 import numpy as np
 
 from .enums import Move, Tile
-from .path import (PATH_UNREACHABLE, PATH_WALL, SEEK_ABSENT, SEEK_COLS, SEEK_UNREACHABLE,
-                   move_toward, room_distance)
-from .query import (MOVE_DELTAS, check_player, check_radius, i64, inside_grid, tile_at,
-                    window_cells)
+from .path import PATH_UNREACHABLE, PATH_WALL, Walk, fill_column, seek_columns
+from .query import bank_of, check_player, check_radius, i64, inside_grid, tile_at, window_cells
 from .sight import SIGHT_SEEN, unpack_rows
 from .view import VIEW_TILE_MASK
 
@@ -109,18 +107,40 @@ def update(memory, key, snap: dict, cfg, player: int, radius: int, rows, cells=N
     return (after - before).astype(np.int32)
 
 
+def remembered(memory, key, snap: dict, cfg, p: int, bank=None):
+    """``(ok, known, tiles)`` of player ``p``'s map: bool [B], where the key is
+    valid for ``snap`` and the player stands in the grid; ``unpack(memory)``,
+    bool [B, W, H]; and the Tile codes [B, W, H] of the dungeon the player is
+    in -- its layout (clamped into the bank) of ``bank``, else the empty
+    room's."""
+    W, H = int(cfg.width), int(cfg.height)
+    ok = valid(key, snap, p) & inside_grid(cfg, i64(snap["p_x"][p]), i64(snap["p_y"][p]))
+    if bank is None:
+        X, Y = (np.broadcast_to(a, (len(ok), W, H)) for a in np.indices((W, H)))
+        tiles = tile_at(cfg, snap, p, X, Y)[1]
+    else:
+        lay = np.clip(i64(snap["p_layout"][p]), 0, len(bank.layouts) - 1)
+        tiles = bank.layouts[lay].astype(np.int64) & 3
+    return ok, unpack(memory, W), tiles
+
+
+def neighbours(cells) -> np.ndarray:
+    """bool [..., W, H]: the in-grid 4-neighbours of bool [..., W, H] cells."""
+    c = np.asarray(cells, bool)
+    out = np.zeros(c.shape, bool)
+    out[..., 1:, :] |= c[..., :-1, :]
+    out[..., :-1, :] |= c[..., 1:, :]
+    out[..., :, 1:] |= c[..., :, :-1]
+    out[..., :, :-1] |= c[..., :, 1:]
+    return out
+
+
 def frontier(known, tiles) -> np.ndarray:
     """bool [..., W, H]: the frontier cells of ``known`` (bool [..., W, H]) on
     ``tiles`` (Tile codes of the same shape): known, Ground, and an in-grid
     4-neighbour that is not known."""
     k = np.asarray(known, bool)
-    un = ~k
-    edge = np.zeros(k.shape, bool)
-    edge[..., 1:, :] |= un[..., :-1, :]
-    edge[..., :-1, :] |= un[..., 1:, :]
-    edge[..., :, 1:] |= un[..., :, :-1]
-    edge[..., :, :-1] |= un[..., :, 1:]
-    return k & (np.asarray(tiles) == int(Tile.Ground)) & edge
+    return k & (np.asarray(tiles) == int(Tile.Ground)) & neighbours(~k)
 
 
 def seek(memory, key, snap: dict, cfg, player: int, bank=None):
@@ -140,67 +160,27 @@ def seek(memory, key, snap: dict, cfg, player: int, bank=None):
             ``dist - 1`` from the target -- a staircase neighbour only if it is
             the target; Stay when ``dist <= 0``"""
     check_player(player)
-    if bank is None and getattr(cfg, "layouts", None) is not None:
-        from .dungeons import DungeonBank
-        bank = DungeonBank(cfg.layouts)
     p = int(player)
+    bank = bank_of(cfg, bank)
     W, H = int(cfg.width), int(cfg.height)
-    WH = W * H
     px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
     B = len(px)
     games = np.arange(B)
-    ok = valid(key, snap, p) & inside_grid(cfg, px, py)
-    known = unpack(memory, W)
-    X = np.broadcast_to(np.arange(W)[None, :, None], (B, W, H))
-    Y = np.broadcast_to(np.arange(H)[None, None, :], (B, W, H))
-    flat = lambda u, v: np.clip(u, 0, W - 1) * H + np.clip(v, 0, H - 1)
-    own = flat(px, py)
-    if bank is None:
-        sx, sy = i64(snap["st_x"][p]), i64(snap["st_y"][p])
-        tiles = tile_at(cfg, snap, p, X, Y)[1]
-        g = (slice(None), None, None)
-        d = room_distance(cfg, sx[g], sy[g], px[g], py[g], X, Y).reshape(B, WH)
-    else:
-        pairs = bank.pair_field()
-        lay = np.clip(i64(snap["p_layout"][p]), 0, len(pairs) - 1)
-        tiles = bank.layouts[lay].astype(np.int64) & 3
-        d = pairs[lay[:, None], np.arange(WH)[None, :], own[:, None]].astype(np.int64)
-    d = np.minimum(d, PATH_UNREACHABLE)
-
-    def between(x, y, tc):
-        """From cells (x, y) to flat target cells ``tc``, int64 [B]."""
-        if bank is None:
-            v = room_distance(cfg, sx, sy, x, y, tc // H, tc % H)
-        else:
-            v = pairs[lay, tc, flat(x, y)].astype(np.int64)
-        return np.where(inside_grid(cfg, x, y), v, PATH_WALL)
-
-    def is_stair(x, y):
-        return inside_grid(cfg, x, y) & (tiles[games, np.clip(x, 0, W - 1), np.clip(y, 0, H - 1)]
-                                         == int(Tile.StaircaseDown))
-
-    dist = np.full((B, SEEK_COLS), SEEK_ABSENT, np.int32)
-    move = np.full((B, SEEK_COLS), int(Move.Stay), np.int8)
-    target = np.full((B, SEEK_COLS), -1, np.int32)
+    ok, known, tiles = remembered(memory, key, snap, cfg, p, bank)
+    walk = Walk(cfg, snap, p, bank)
+    X, Y = (np.broadcast_to(a, (B, W, H)) for a in np.indices((W, H)))
+    d = np.minimum(walk.between(px[:, None, None], py[:, None, None], X, Y), PATH_UNREACHABLE)
+    out = seek_columns((B,), np.int32)
     columns = ((EXPLORE_FRONTIER, frontier(known, tiles)),
                (EXPLORE_STAIRS, known & (tiles == int(Tile.StaircaseDown))))
     for col, cells in columns:
         # absent above unreachable above every distance: argmin takes the lowest cell
-        v = np.where(cells.reshape(B, WH) & ok[:, None], d, PATH_WALL)
+        v = np.where(cells & ok[:, None, None], d, PATH_WALL).reshape(B, W * H)
         best = v.argmin(axis=1)
-        here = v[games, best]
-        has = here != PATH_WALL
-        bx, by = best // H, best % H
-        near = []
-        for _, dx, dy in MOVE_DELTAS:
-            x, y = px + dx, py + dy
-            near.append(np.where(is_stair(x, y) & ~((x == bx) & (y == by)), PATH_WALL,
-                                 between(x, y, best)))
-        dist[:, col] = np.where(has, np.where(here == PATH_UNREACHABLE, SEEK_UNREACHABLE, here),
-                                SEEK_ABSENT)
-        move[:, col] = np.where(has, move_toward(here, *near), int(Move.Stay))
-        target[:, col] = np.where(has, best, -1)
-    return dist, move, target
+        own = v[games, best]
+        fill_column(out, col, own != PATH_WALL, own,
+                    walk.first_move(px, py, best // H, best % H, own), best)
+    return out
 
 
 def explorer_moves(dist, move) -> np.ndarray:

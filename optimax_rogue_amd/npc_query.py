@@ -28,9 +28,8 @@ from .enums import (DungeonDespawningStrategy, Move, NPC_DEPTH_GONE, NPC_DEPTH_U
                     NPC_OUT_FROZEN, NPC_OUT_LETHAL, NPC_OUT_MASK, NPC_OUT_NONE, NPC_OUT_REST,
                     NPC_OUT_STAIRS, NPC_OUT_STEP, NPC_SEEK_NEAREST, Tile)
 from .moves import MOVES_COLS
-from .path import (PATH_UNREACHABLE, PATH_WALL, SEEK_ABSENT, SEEK_COLS, SEEK_UNREACHABLE,
-                   move_toward, room_distance)
-from .query import MOVE_DELTAS, i64, inside_grid, npc_depth, npc_rows, tile_at
+from .path import PATH_UNREACHABLE, PATH_WALL, Walk, fill_column, seek_columns
+from .query import MOVE_DELTAS, bank_of, i64, inside_grid, npc_depth, npc_rows, tile_at
 
 
 def _check(cfg) -> int:
@@ -43,9 +42,7 @@ def _check(cfg) -> int:
 def _layouts(cfg, bank):
     """``(bank, layouts)``: the DungeonBank of a configuration with one (made
     from ``cfg.layouts`` when omitted) and its [L, W, H] Tile codes."""
-    if bank is None and getattr(cfg, "layouts", None) is not None:
-        from .dungeons import DungeonBank
-        bank = DungeonBank(cfg.layouts)
+    bank = bank_of(cfg, bank)
     return bank, None if bank is None else np.asarray(bank.layouts)
 
 
@@ -181,59 +178,26 @@ def seek(snap: dict, cfg, bank=None):
     target  the player's iden, 1 or 2; -1 when absent"""
     K = _check(cfg)
     bank, layouts = _layouts(cfg, bank)
-    W, H = int(cfg.width), int(cfg.height)
     nd = npc_depth(cfg)
     watched = depth_state(snap, cfg) == NPC_DEPTH_WATCHED
-    B = len(watched)
-    dung = _depth_dungeon(snap, cfg, layouts)
+    walk = Walk(cfg, _depth_dungeon(snap, cfg, layouts), 0, bank)
     px, py, pd = (i64(snap[f]) for f in ("p_x", "p_y", "p_depth"))
     alive, nx, ny, _ = (a.T for a in npc_rows(snap, K))               # [B, K]
-    if bank is not None:
-        pairs = bank.pair_field()
-        lay = np.clip(dung["p_layout"][0], 0, len(pairs) - 1)[:, None]
-
-    def between(x, y, tx, ty):
-        """The distance between cells (x, y) and (tx, ty), int64 [B, K]."""
-        inside = inside_grid(cfg, x, y) & inside_grid(cfg, tx, ty)
-        if bank is None:
-            v = room_distance(cfg, dung["st_x"][0][:, None], dung["st_y"][0][:, None], x, y, tx, ty)
-        else:
-            flat = lambda u, v: np.clip(u, 0, W - 1) * H + np.clip(v, 0, H - 1)
-            v = pairs[lay, flat(tx, ty), flat(x, y)].astype(np.int64)
-        return np.where(inside & (v < PATH_UNREACHABLE), v, PATH_UNREACHABLE)
-
-    def is_stair(x, y):
-        inside, tile = tile_at(cfg, dung, 0, x, y, layouts)
-        return inside & (tile == int(Tile.StaircaseDown))
-
-    no_path, absent = 0x7FFFFFFF, 0xFFFFFFFF   # absent above unreachable above every distance
-    reach = np.full((2, B, K), absent, np.int64)
-    move = np.full((2, B, K), int(Move.Stay), np.int8)
     here = alive & watched[:, None] & inside_grid(cfg, nx, ny)
+    has, own, move = [], [], []
     for p in (0, 1):
-        tx, ty = px[p][:, None] + 0 * nx, py[p][:, None] + 0 * ny
-        own = between(nx, ny, tx, ty)
-        near = []
-        for _, dx, dy in MOVE_DELTAS:
-            x, y = nx + dx, ny + dy
-            near.append(np.where(is_stair(x, y) & ~((x == tx) & (y == ty)), PATH_WALL,
-                                 between(x, y, tx, ty)))
-        has = here & (pd[p] == nd)[:, None]
-        reach[p] = np.where(has, np.where(own == PATH_UNREACHABLE, no_path, own), absent)
-        move[p] = np.where(has, move_toward(own, *near), int(Move.Stay))
-    nearer = (reach[1] < reach[0]).astype(np.int64)
-    dist = np.full((B, K, SEEK_COLS), SEEK_ABSENT, np.int32)
-    mv = np.full((B, K, SEEK_COLS), int(Move.Stay), np.int8)
-    target = np.full((B, K, SEEK_COLS), -1, np.int16)
+        tx, ty = px[p][:, None], py[p][:, None]
+        has.append(here & (pd[p] == nd)[:, None])
+        own.append(np.minimum(walk.between(nx, ny, tx, ty), PATH_UNREACHABLE))
+        move.append(walk.first_move(nx, ny, tx, ty, own[p]))
+    # absent above unreachable above every distance; player 1 wins a tie
+    nearer = np.where(has[1], own[1], PATH_WALL) < np.where(has[0], own[0], PATH_WALL)
+    out = seek_columns(nx.shape, np.int16)
     for col in range(NPC_SEEK_NEAREST + 1):
-        p = np.full((B, K), col) if col < NPC_SEEK_NEAREST else nearer
-        r = np.where(p == 0, reach[0], reach[1])
-        dist[:, :, col] = np.where(r == absent, SEEK_ABSENT,
-                                   np.where(r == no_path, SEEK_UNREACHABLE, r))
-        mv[:, :, col] = np.where(p == 0, move[0], move[1])
-        target[:, :, col] = np.where(r == absent, -1, p + 1)
-    t = lambda a: np.ascontiguousarray(a.transpose(1, 0, 2))
-    return t(dist), t(mv), t(target)
+        p = np.full(nx.shape, col) if col < NPC_SEEK_NEAREST else nearer.astype(np.int64)
+        pick = lambda pair: np.where(p == 0, pair[0], pair[1])
+        fill_column(out, col, pick(has), pick(own), pick(move), p + 1)
+    return tuple(np.ascontiguousarray(a.transpose(1, 0, 2)) for a in out)
 
 
 def hunt_moves(kind, move, target=None) -> np.ndarray:

@@ -32,8 +32,8 @@ from __future__ import annotations
 import numpy as np
 
 from .enums import Move, Tile
-from .query import (MOVE_DELTAS, bank_at, check_player, check_radius, i64, inside_grid, item_rows,
-                    npc_depth, npc_rows, tile_at, window_cells)
+from .query import (MOVE_DELTAS, bank_at, bank_of, check_player, check_radius, i64, inside_grid,
+                    item_rows, npc_depth, npc_rows, per_game, tile_at, window_cells)
 
 # include/orx_path.h ORX_PATH_* and ORX_SEEK_*
 PATH_WALL = 0xFFFF
@@ -131,9 +131,7 @@ def query(snap: dict, cfg, player: int, radius=None, bank=None):
     a bank (made from ``cfg.layouts`` when omitted), else ``closed_form`` with
     the staircase (st_x, st_y)[player] of the player's depth."""
     check_path_args(player, radius, cfg)
-    if bank is None and getattr(cfg, "layouts", None) is not None:
-        from .dungeons import DungeonBank
-        bank = DungeonBank(cfg.layouts)
+    bank = bank_of(cfg, bank)
     p = int(player)
     px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
     if bank is None:
@@ -241,6 +239,68 @@ def room_distance(cfg, sx, sy, ax, ay, bx, by) -> np.ndarray:
     return np.where(inner(ax, ay) & inner(bx, by), d, PATH_WALL)
 
 
+# -- what the seek-shaped queries share (the host twin of csrc/orx_seek.h) -----
+class Walk:
+    """The dungeon that row ``p`` of a ``snapshot()``-shaped dict walks on: the
+    layout ``p_layout[p]`` (clamped into the bank) of ``bank``, else
+    EmptyDungeonGenerator's room with its staircase at (st_x, st_y)[p].  Cells
+    are int64 arrays [B, ...] that broadcast, the games on the first axis."""
+
+    def __init__(self, cfg, snap: dict, p: int, bank=None):
+        self.cfg, self.snap, self.p, self.bank = cfg, snap, p, bank
+        if bank is not None:
+            self.pairs = bank.pair_field()
+            self.lay = np.clip(i64(snap["p_layout"][p]), 0, len(self.pairs) - 1)
+
+    def between(self, x, y, tx, ty):
+        """The walking distance between cells (x, y) and (tx, ty): the pair
+        table, else ``room_distance``; PATH_WALL where either is off the grid."""
+        W, H = int(self.cfg.width), int(self.cfg.height)
+        x, y, tx, ty = np.broadcast_arrays(x, y, tx, ty)
+        if self.bank is None:
+            sx, sy = (per_game(i64(self.snap[f][self.p]), x) for f in ("st_x", "st_y"))
+            v = room_distance(self.cfg, sx, sy, x, y, tx, ty)
+        else:
+            flat = lambda u, v: np.clip(u, 0, W - 1) * H + np.clip(v, 0, H - 1)
+            v = self.pairs[per_game(self.lay, x), flat(tx, ty), flat(x, y)].astype(np.int64)
+        return np.where(inside_grid(self.cfg, x, y) & inside_grid(self.cfg, tx, ty), v, PATH_WALL)
+
+    def is_stair(self, x, y):
+        inside, tile = tile_at(self.cfg, self.snap, self.p, x, y,
+                               None if self.bank is None else self.bank.layouts)
+        return inside & (tile == int(Tile.StaircaseDown))
+
+    def first_move(self, x, y, tx, ty, own):
+        """int8: from cells (x, y) at distance ``own`` from their targets (tx,
+        ty), the first of Up, Right, Down, Left whose neighbour cell is at
+        ``own - 1`` -- a staircase neighbour only if it is the target's own
+        cell (``move_toward``)."""
+        near = []
+        for _, dx, dy in MOVE_DELTAS:
+            nx, ny = x + dx, y + dy
+            near.append(np.where(self.is_stair(nx, ny) & ~((nx == tx) & (ny == ty)), PATH_WALL,
+                                 self.between(nx, ny, tx, ty)))
+        return move_toward(own, *near)
+
+
+def seek_columns(shape, target_dtype):
+    """``(dist, move, target)`` [*shape, SEEK_COLS] with every column absent."""
+    shape = tuple(shape) + (SEEK_COLS,)
+    return (np.full(shape, SEEK_ABSENT, np.int32), np.full(shape, int(Move.Stay), np.int8),
+            np.full(shape, -1, target_dtype))
+
+
+def fill_column(out, col: int, has, own, move, chosen) -> None:
+    """Column ``col`` of ``out = (dist, move, target)``: where the column ``has``
+    a target, its distance ``own`` (SEEK_UNREACHABLE from PATH_UNREACHABLE up),
+    ``move`` and the ``chosen`` slot or cell; elsewhere SEEK_ABSENT, Stay, -1."""
+    dist, mv, target = out
+    dist[..., col] = np.where(has, np.where(own >= PATH_UNREACHABLE, SEEK_UNREACHABLE, own),
+                              SEEK_ABSENT)
+    mv[..., col] = np.where(has, move, int(Move.Stay))
+    target[..., col] = np.where(has, chosen, -1)
+
+
 def seek(snap: dict, cfg, player: int, bank=None):
     """``(dist, move, target)``, int32, int8 and int16 [B, SEEK_COLS], of
     ``player`` (0 / 1) of every game of a ``snapshot()``-shaped dict: column
@@ -259,34 +319,12 @@ def seek(snap: dict, cfg, player: int, bank=None):
             ``dist - 1`` from that target -- a staircase neighbour only if it
             is the target's own cell; Stay when ``dist <= 0``"""
     check_player(player)
-    if bank is None and getattr(cfg, "layouts", None) is not None:
-        from .dungeons import DungeonBank
-        bank = DungeonBank(cfg.layouts)
     p, q = int(player), 1 - int(player)
-    W, H, K = int(cfg.width), int(cfg.height), int(cfg.n_npcs)
+    K = int(cfg.n_npcs)
+    walk = Walk(cfg, snap, p, bank_of(cfg, bank))
     px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
     B = len(px)
     depth = i64(snap["p_depth"][p])
-    if bank is None:
-        sx, sy = i64(snap["st_x"][p]), i64(snap["st_y"][p])
-    else:
-        pairs = bank.pair_field()
-        lay = np.clip(i64(snap["p_layout"][p]), 0, len(pairs) - 1)
-
-    def between(x, y, tx, ty):
-        """The distance between cells (x, y) and (tx, ty), int64 [..., B]."""
-        inside = inside_grid(cfg, x, y) & inside_grid(cfg, tx, ty)
-        if bank is None:
-            v = room_distance(cfg, sx, sy, x, y, tx, ty)
-        else:
-            flat = lambda u, v: np.clip(u, 0, W - 1) * H + np.clip(v, 0, H - 1)
-            v = pairs[lay, flat(tx, ty), flat(x, y)].astype(np.int64)
-        return np.where(inside, v, PATH_WALL)
-
-    def is_stair(x, y):
-        inside, tile = tile_at(cfg, snap, p, x, y, None if bank is None else bank.layouts)
-        return inside & (tile == int(Tile.StaircaseDown))
-
     here = inside_grid(cfg, px, py)
     on_npc_depth = here & (depth == npc_depth(cfg))
     columns = [((here & (i64(snap["p_depth"][q]) == depth))[None],
@@ -297,24 +335,15 @@ def seek(snap: dict, cfg, player: int, bank=None):
         if snap.get("item_mask") is not None:
             on, ix, iy, _ = item_rows(snap, K)
             columns.append((on & on_npc_depth, ix, iy, np.arange(K)))
-    dist = np.full((B, SEEK_COLS), SEEK_ABSENT, np.int32)
-    move = np.full((B, SEEK_COLS), int(Move.Stay), np.int8)
-    target = np.full((B, SEEK_COLS), -1, np.int16)
+    out = seek_columns((B,), np.int16)
     games = np.arange(B)
     for col, (present, tx, ty, slots) in enumerate(columns):
         # absent above unreachable above every distance: argmin takes the lowest slot
-        v = between(px, py, tx, ty)
-        v = np.where(present, np.where(v >= PATH_UNREACHABLE, PATH_UNREACHABLE, v), PATH_WALL)
-        best = v.argmin(axis=0)
-        own, bx, by = v[best, games], tx[best, games], ty[best, games]
-        has = own != PATH_WALL
-        near = []
-        for _, dx, dy in MOVE_DELTAS:
-            x, y = px + dx, py + dy
-            near.append(np.where(is_stair(x, y) & ~((x == bx) & (y == by)), PATH_WALL,
-                                 between(x, y, bx, by)))
-        dist[:, col] = np.where(has, np.where(own == PATH_UNREACHABLE, SEEK_UNREACHABLE, own),
-                                SEEK_ABSENT)
-        move[:, col] = np.where(has, move_toward(own, *near), int(Move.Stay))
-        target[:, col] = np.where(has, slots[best], -1)
-    return dist, move, target
+        present, tx, ty = present.T, tx.T, ty.T                      # [B, slots]
+        v = np.minimum(walk.between(px[:, None], py[:, None], tx, ty), PATH_UNREACHABLE)
+        v = np.where(present, v, PATH_WALL)
+        best = v.argmin(axis=1)
+        own, bx, by = v[games, best], tx[games, best], ty[games, best]
+        fill_column(out, col, own != PATH_WALL, own, walk.first_move(px, py, bx, by, own),
+                    slots[best])
+    return out

@@ -1,6 +1,7 @@
 """What ``view.render_view``, ``path.query`` and ``moves.outcomes`` share (the
 host twin of csrc/orx_query.h): the argument checks, the window's coordinates,
 the tile of a cell and the NPC and item rows of a ``snapshot()``-shaped dict.
+(The twin of csrc/orx_seek.h is ``path.Walk`` and its column helpers.)
 """
 from __future__ import annotations
 
@@ -30,6 +31,15 @@ def check_radius(radius) -> None:
         raise ValueError(f"radius must be an integer in [1, {MAX_RADIUS}], got {radius!r}")
 
 
+def bank_of(cfg, bank=None):
+    """``bank``, or the DungeonBank made from ``cfg.layouts`` where the
+    configuration has layouts and none is given; None without layouts."""
+    if bank is None and getattr(cfg, "layouts", None) is not None:
+        from .dungeons import DungeonBank
+        bank = DungeonBank(cfg.layouts)
+    return bank
+
+
 def npc_depth(cfg) -> int:
     """The depth the NPCs (and their items) are on: player 1's start depth."""
     return int(cfg.p1_depth) if int(cfg.start_mode) == StartMode.Separated else 0
@@ -44,7 +54,7 @@ def window_cells(px, py, radius: int):
             np.broadcast_to(py[:, None, None] + off[None, :, None], shape))
 
 
-def _per_game(a, cells):   # [B] -> [B, 1, ...] against cells of shape [B, ...]
+def per_game(a, cells):   # [B] -> [B, 1, ...] against cells of shape [B, ...]
     return a[(slice(None),) + (None,) * (cells.ndim - 1)]
 
 
@@ -57,7 +67,7 @@ def bank_at(planes, snap: dict, p: int, x, y):
     into the grid, on player row ``p``'s layout (clamped as the kernels do)."""
     L, W, H = planes.shape
     lay = np.clip(i64(snap["p_layout"][p]), 0, L - 1)
-    return planes[_per_game(lay, x), np.clip(x, 0, W - 1), np.clip(y, 0, H - 1)]
+    return planes[per_game(lay, x), np.clip(x, 0, W - 1), np.clip(y, 0, H - 1)]
 
 
 def tile_at(cfg, snap: dict, p: int, x, y, layouts=None, stair_on_border: bool = False):
@@ -71,7 +81,7 @@ def tile_at(cfg, snap: dict, p: int, x, y, layouts=None, stair_on_border: bool =
         return inside, bank_at(np.asarray(layouts), snap, p, x, y).astype(np.int64) & 3
     W, H = int(cfg.width), int(cfg.height)
     wall = (x == 0) | (x == W - 1) | (y == 0) | (y == H - 1)
-    stair = (x == _per_game(i64(snap["st_x"][p]), x)) & (y == _per_game(i64(snap["st_y"][p]), x))
+    stair = (x == per_game(i64(snap["st_x"][p]), x)) & (y == per_game(i64(snap["st_y"][p]), x))
     if not stair_on_border:
         stair = stair & ~wall
     return inside, np.where(stair, int(Tile.StaircaseDown),

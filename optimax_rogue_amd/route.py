@@ -18,9 +18,9 @@ from __future__ import annotations
 import numpy as np
 
 from .enums import Move, Tile
-from .explore import frontier, pack, unpack, valid
-from .path import SEEK_ABSENT, SEEK_COLS, SEEK_UNREACHABLE
-from .query import MOVE_DELTAS, check_player, i64, inside_grid, tile_at
+from .explore import frontier, neighbours, pack, remembered
+from .path import SEEK_ABSENT, SEEK_UNREACHABLE, seek_columns
+from .query import MOVE_DELTAS, bank_of, check_player, i64, inside_grid
 
 # include/orx_route.h
 ROUTE_FRONTIER, ROUTE_STAIRS, ROUTE_GOAL = 0, 1, 2
@@ -36,16 +36,6 @@ def planes(layouts) -> np.ndarray:
     return np.stack([pack(t == int(Tile.Ground)), pack(t == int(Tile.StaircaseDown))], axis=1)
 
 
-def _dilate(cells) -> np.ndarray:
-    """The 4-neighbours of bool [B, W, H] cells, inside the grid."""
-    out = np.zeros_like(cells)
-    out[:, 1:, :] |= cells[:, :-1, :]
-    out[:, :-1, :] |= cells[:, 1:, :]
-    out[:, :, 1:] |= cells[:, :, :-1]
-    out[:, :, :-1] |= cells[:, :, 1:]
-    return out
-
-
 def known_distance(source, passable, ends) -> np.ndarray:
     """int64 [B, W, H]: the known distance from the ``source`` cell of every
     game (bool [B, W, H], at most one per game; distance 0) to every cell of
@@ -58,7 +48,7 @@ def known_distance(source, passable, ends) -> np.ndarray:
     for k in range(1, source.shape[1] * source.shape[2] + 1):   # (no walk is longer)
         if not wave.any():
             break
-        new = _dilate(wave) & allowed & (dist == _FAR)
+        new = neighbours(wave) & allowed & (dist == _FAR)
         dist[new] = k
         wave = new & passable
     return dist
@@ -84,24 +74,14 @@ def route(memory, key, snap: dict, cfg, player: int, goal=None, bank=None):
             grid, is known Ground or the target itself, and is at known
             distance ``dist - 1`` from the target; Stay when ``dist <= 0``"""
     check_player(player)
-    if bank is None and getattr(cfg, "layouts", None) is not None:
-        from .dungeons import DungeonBank
-        bank = DungeonBank(cfg.layouts)
     p = int(player)
     W, H = int(cfg.width), int(cfg.height)
     WH = W * H
     px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
     B = len(px)
     games = np.arange(B)
-    ok = valid(key, snap, p) & inside_grid(cfg, px, py)
-    known = unpack(memory, W)
-    X = np.broadcast_to(np.arange(W)[None, :, None], (B, W, H))
-    Y = np.broadcast_to(np.arange(H)[None, None, :], (B, W, H))
-    if bank is None:
-        tiles = tile_at(cfg, snap, p, X, Y)[1]
-    else:
-        lay = np.clip(i64(snap["p_layout"][p]), 0, len(bank.layouts) - 1)
-        tiles = bank.layouts[lay].astype(np.int64) & 3
+    ok, known, tiles = remembered(memory, key, snap, cfg, p, bank_of(cfg, bank))
+    X, Y = (np.broadcast_to(a, (B, W, H)) for a in np.indices((W, H)))
     passable = known & (tiles == int(Tile.Ground))
     stairs = known & (tiles == int(Tile.StaircaseDown))
     ends = passable | stairs                      # where a known walk may end
@@ -120,9 +100,7 @@ def route(memory, key, snap: dict, cfg, player: int, goal=None, bank=None):
         gin = (g >= 0) & (g < WH)
         goals = one(np.where(gin, g // H, -1), np.where(gin, g % H, -1))
 
-    dist = np.full((B, SEEK_COLS), SEEK_ABSENT, np.int32)
-    move = np.full((B, SEEK_COLS), int(Move.Stay), np.int8)
-    target = np.full((B, SEEK_COLS), -1, np.int32)
+    dist, move, target = seek_columns((B,), np.int32)
     columns = ((ROUTE_FRONTIER, frontier(known, tiles)), (ROUTE_STAIRS, stairs), (ROUTE_GOAL, goals))
     for col, cells in columns:
         cells = cells & ok[:, None, None]

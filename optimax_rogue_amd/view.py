@@ -26,8 +26,8 @@ from __future__ import annotations
 import numpy as np
 
 from .enums import EXT_ITEMS, Tile
-from .query import (MAX_RADIUS, check_player, check_radius, i64, item_rows, npc_depth,  # noqa: F401
-                    npc_rows, tile_at, window_cells)
+from .query import (MAX_RADIUS, bank_of, check_player, check_radius, i64, item_rows,  # noqa: F401
+                    npc_depth, npc_rows, tile_at, window_cells)
 
 # include/orx_view.h ORX_VIEW_*
 VIEW_MAX_RADIUS = MAX_RADIUS
@@ -57,9 +57,7 @@ def render_view(snap: dict, cfg, player: int, radius: int, bank=None, health: bo
     check_view_args(player, radius)
     W, H, K, R = int(cfg.width), int(cfg.height), int(cfg.n_npcs), int(radius)
     V = 2 * R + 1
-    if bank is None and getattr(cfg, "layouts", None) is not None:
-        from .dungeons import DungeonBank
-        bank = DungeonBank(cfg.layouts)
+    bank = bank_of(cfg, bank)
     p, q = int(player), 1 - int(player)
     px, py, d = i64(snap["p_x"][p]), i64(snap["p_y"][p]), i64(snap["p_depth"][p])
     B = len(px)

@@ -18,7 +18,6 @@ change 916, by an episode change 800; known-but-unseen window cells 12,504;
 updates that gained something 7,348, nothing 16,652; staircase known 12,084,
 not yet known 11,916.
 """
-import hashlib
 import os
 import re
 import subprocess
@@ -306,40 +305,10 @@ def test_header_is_the_export_table():
     decl = sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(orx_\w+)\s*\(", text, re.M)))
     assert decl == sorted(_lib.EXPLORE_EXPORTS) \
         == ["orx_explore_build_id", "orx_explore_seek", "orx_explore_update"]
-    assert not set(_lib.EXPLORE_EXPORTS) & (
-        set(_lib.EXPORTS) | set(_lib.VIEW_EXPORTS) | set(_lib.PATH_EXPORTS)
-        | set(_lib.MOVES_EXPORTS) | set(_lib.NPC_EXPORTS) | set(_lib.NPC_QUERY_EXPORTS)
-        | set(_lib.SIGHT_EXPORTS))
     for hdr in ("orx.h", "orx_view.h"):
         with open(os.path.join(ROOT, "include", hdr)) as f:
             assert "orx_explore" not in f.read()
     assert _lib.ABI_VERSION == 7
-
-
-def test_explore_symbols_and_build_id(engine_lib):
-    """The library exports the header's entry points; its explore id is the
-    hash of orx_explore.hip, orx_explore.h, orx_query.h and orx_seek.h and
-    shows only under ``every=True``."""
-    from optimax_rogue_amd import _lib, build
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
-                         text=True, check=True).stdout
-    assert set(_lib.EXPLORE_EXPORTS) <= set(re.findall(r" T (orx_\w+)", out))
-    for name in _lib.EXPLORE_EXPORTS:
-        assert hasattr(engine_lib, name)
-    src = os.path.join(ROOT, "optimax_rogue_amd", "csrc", "orx_explore.hip")
-    hdr = os.path.join(ROOT, "include", "orx_explore.h")
-    assert (src, hdr) == (build.EXPLORE_SRC, build.EXPLORE_HDR)
-    h = hashlib.sha256()
-    for p in (src, hdr, build.QUERY_HDR, build.SEEK_HDR):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    assert build.explore_id() == h.hexdigest()[:16] == _lib.explore_build_id()
-    assert build.PARTS["explore"] == build.Part("orx_explore_build_id", "ORX_EXPLORE_BUILD_ID",
-                                                (src, hdr, build.QUERY_HDR, build.SEEK_HDR), ())
-    assert src in build.EXTRA_SOURCES and src in build.SOURCES
-    ids = build.built_ids(_lib.LIB_PATH, every=True)
-    assert ids == build.tree_ids() and ids["explore"] == build.explore_id()
-    assert set(build.built_ids(_lib.LIB_PATH)) == {"engine", "path", "moves"}
 
 
 def test_explore_header_in_a_plain_c_consumer(engine_lib, tmp_path):

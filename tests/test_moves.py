@@ -103,34 +103,9 @@ def test_header_constants_are_the_modules():
     assert (defs["ORX_OUT_LETHAL"], defs["ORX_OUT_ITEM"], defs["ORX_OUT_COOLDOWN"]) == (8, 16, 32)
     decl = sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(orx_\w+)\s*\(", text, re.M)))
     assert decl == sorted(_lib.MOVES_EXPORTS)
-    assert not set(_lib.MOVES_EXPORTS) & (set(_lib.EXPORTS) | set(_lib.VIEW_EXPORTS)
-                                          | set(_lib.PATH_EXPORTS))
     # orx.h is what it was: the new entry points are not declared there
     with open(os.path.join(ROOT, "include", "orx.h")) as f:
         assert "orx_moves" not in f.read()
-
-
-def test_moves_symbols_and_build_id(engine_lib):
-    """The library exports the header's entry points, and its moves id is the
-    hash of the tree's orx_moves.hip, orx_moves.h and the queries' shared
-    header (a stale library is rebuilt: build.build compares all three ids)."""
-    import hashlib
-    import subprocess
-    from optimax_rogue_amd import _lib, build
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
-                         text=True, check=True).stdout
-    assert set(_lib.MOVES_EXPORTS) <= set(re.findall(r" T (orx_\w+)", out))
-    for name in _lib.MOVES_EXPORTS:
-        assert hasattr(engine_lib, name)
-    h = hashlib.sha256()
-    for p in (build.MOVES_SRC, build.MOVES_HDR, build.QUERY_HDR):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    assert build.moves_id() == h.hexdigest()[:16] == _lib.moves_build_id()
-    assert build.built_ids(_lib.LIB_PATH) == {"engine": build.source_id(), "path": build.path_id(),
-                                              "moves": build.moves_id()}
-    assert os.path.basename(build.MOVES_SRC) == "orx_moves.hip"
-    assert os.path.basename(build.MOVES_HDR) == "orx_moves.h"
 
 
 def test_moves_header_in_a_plain_c_consumer(engine_lib, tmp_path):

@@ -2,7 +2,6 @@
 restatement against the reference's fixtures, the header against the export
 table and the library, the build id, and the host-side refusals from a plain
 C consumer."""
-import hashlib
 import os
 import re
 import subprocess
@@ -81,39 +80,9 @@ def test_header_is_the_export_table():
         text = f.read()
     decl = sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(orx_\w+)\s*\(", text, re.M)))
     assert decl == sorted(_lib.NPC_EXPORTS) and len(decl) == 6
-    assert not set(_lib.NPC_EXPORTS) & (set(_lib.EXPORTS) | set(_lib.VIEW_EXPORTS)
-                                        | set(_lib.PATH_EXPORTS) | set(_lib.MOVES_EXPORTS))
     # orx.h is what it was: the new entry points are not declared there
     with open(os.path.join(ROOT, "include", "orx.h")) as f:
         assert "orx_npc_" not in f.read()
-
-
-def test_npc_symbols_and_build_id(engine_lib):
-    """The library exports the header's entry points; its npc id is the hash
-    of orx_npc.h and orx_engine.hip, and the engine id still the hash of the
-    six files it always named (the new header is not among them)."""
-    from optimax_rogue_amd import _lib, build
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
-                         text=True, check=True).stdout
-    assert set(_lib.NPC_EXPORTS) <= set(re.findall(r" T (orx_\w+)", out))
-    for name in _lib.NPC_EXPORTS:
-        assert hasattr(engine_lib, name)
-
-    def digest(paths):
-        h = hashlib.sha256()
-        for p in paths:
-            with open(p, "rb") as f:
-                h.update(f.read())
-        return h.hexdigest()[:16]
-    hdr = os.path.join(ROOT, "include", "orx_npc.h")
-    assert build.npc_id() == digest((hdr, build.SRC)) == _lib.npc_build_id()
-    assert engine_lib.orx_npc_build_id().decode() == build.npc_id()
-    assert build.source_id() == digest((build.SRC, build.HDR, build.VIEW_SRC, build.VIEW_HDR,
-                                        build.QUERY_HDR, build.PLAN_HDR)) == _lib.build_id()
-    part = build.PARTS["npc"]
-    assert part.symbol == "orx_npc_build_id" and part.macro == "ORX_NPC_BUILD_ID"
-    assert part.files == (hdr, build.SRC) and part.sources == ()
-    assert build.built_ids(_lib.LIB_PATH, every=True)["npc"] == build.npc_id()
 
 
 def test_npc_header_in_a_plain_c_consumer(engine_lib, tmp_path):

@@ -4,7 +4,6 @@ reference fixtures pin, against the CPU restatement of the tick move by move,
 against ``path.seek`` from the players' side and against hand-built states;
 the header against the export table and the library, the build id, and the
 host-side refusals from a plain C consumer."""
-import hashlib
 import os
 import re
 import subprocess
@@ -212,52 +211,11 @@ def test_header_is_the_export_table():
     assert [defs["NPC_OUT_" + n] for n in enums.NPC_OUT_NAMES] == list(range(8))
     decl = sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(orx_\w+)\s*\(", text, re.M)))
     assert decl == sorted(_lib.NPC_QUERY_EXPORTS) and len(decl) == 3
-    assert not set(_lib.NPC_QUERY_EXPORTS) & (
-        set(_lib.EXPORTS) | set(_lib.VIEW_EXPORTS) | set(_lib.PATH_EXPORTS)
-        | set(_lib.MOVES_EXPORTS) | set(_lib.NPC_EXPORTS))
     # orx.h and orx_npc.h are what they were, and the ABI version with them
     for hdr in ("orx.h", "orx_npc.h"):
         with open(os.path.join(ROOT, "include", hdr)) as f:
             assert "orx_npc_options" not in f.read()
     assert _lib.ABI_VERSION == 7
-
-
-def test_npc_query_symbols_and_build_id(engine_lib):
-    """The library exports the header's entry points; its npc_query id is the
-    hash of orx_npc_query.hip, orx_npc_query.h, orx_query.h and orx_seek.h and
-    shows only under ``every=True``; the parts that were there name their own
-    files (path with orx_seek.h, which it shares)."""
-    from optimax_rogue_amd import _lib, build
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
-                         text=True, check=True).stdout
-    assert set(_lib.NPC_QUERY_EXPORTS) <= set(re.findall(r" T (orx_\w+)", out))
-    for name in _lib.NPC_QUERY_EXPORTS:
-        assert hasattr(engine_lib, name)
-
-    def digest(paths):
-        h = hashlib.sha256()
-        for p in paths:
-            with open(p, "rb") as f:
-                h.update(f.read())
-        return h.hexdigest()[:16]
-    src = os.path.join(ROOT, "optimax_rogue_amd", "csrc", "orx_npc_query.hip")
-    hdr = os.path.join(ROOT, "include", "orx_npc_query.h")
-    files = (src, hdr, build.QUERY_HDR, build.SEEK_HDR)
-    assert build.npc_query_id() == digest(files) == _lib.npc_query_build_id()
-    part = build.PARTS["npc_query"]
-    assert part.symbol == "orx_npc_query_build_id" and part.macro == "ORX_NPC_QUERY_BUILD_ID"
-    assert part.files == files and part.sources == ()
-    assert src in build.SOURCES and build.SOURCES[0] == build.SRC
-    ids = build.built_ids(_lib.LIB_PATH, every=True)
-    assert ids == build.tree_ids() and ids["npc_query"] == build.npc_query_id()
-    assert set(build.built_ids(_lib.LIB_PATH)) == {"engine", "path", "moves"}
-    # the files of the parts that were there are the files they were
-    assert build.PARTS["engine"].files == (build.SRC, build.HDR, build.VIEW_SRC, build.VIEW_HDR,
-                                           build.QUERY_HDR, build.PLAN_HDR)
-    assert build.PARTS["path"].files == (build.PATH_SRC, build.PATH_HDR, build.QUERY_HDR,
-                                         build.SEEK_HDR)
-    assert build.PARTS["moves"].files == (build.MOVES_SRC, build.MOVES_HDR, build.QUERY_HDR)
-    assert build.PARTS["npc"].files == (build.NPC_HDR, build.SRC)
 
 
 def test_npc_query_header_in_a_plain_c_consumer(engine_lib, tmp_path):

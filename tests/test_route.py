@@ -16,7 +16,6 @@ them: on the 12 x 10 radius-1 explorer run, state-games whose stairs distance
 exceeds the seek's; state-games with no frontier left to walk to and a
 staircase known; every goal class hit on the oracle runs.
 """
-import hashlib
 import os
 import re
 import subprocess
@@ -433,40 +432,10 @@ def test_header_is_the_export_table():
     assert '#include "orx_explore.h"' in text and "P1." in text and "P2." in text
     decl = sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(orx_\w+)\s*\(", text, re.M)))
     assert decl == sorted(_lib.ROUTE_EXPORTS) == ["orx_route", "orx_route_build_id", "orx_route_planes"]
-    assert not set(_lib.ROUTE_EXPORTS) & (
-        set(_lib.EXPORTS) | set(_lib.VIEW_EXPORTS) | set(_lib.PATH_EXPORTS)
-        | set(_lib.MOVES_EXPORTS) | set(_lib.NPC_EXPORTS) | set(_lib.NPC_QUERY_EXPORTS)
-        | set(_lib.SIGHT_EXPORTS) | set(_lib.EXPLORE_EXPORTS))
     for hdr in ("orx.h", "orx_view.h", "orx_explore.h"):
         with open(os.path.join(ROOT, "include", hdr)) as f:
             assert "orx_route" not in f.read()
     assert _lib.ABI_VERSION == 7 and optimax_rogue_amd.route is route
-
-
-def test_route_symbols_and_build_id(engine_lib):
-    """The library exports the header's entry points; its route id is the hash
-    of orx_route.hip, orx_route.h, orx_query.h and orx_seek.h and shows only under
-    ``every=True``."""
-    from optimax_rogue_amd import _lib, build
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
-                         text=True, check=True).stdout
-    assert set(_lib.ROUTE_EXPORTS) <= set(re.findall(r" T (orx_\w+)", out))
-    for name in _lib.ROUTE_EXPORTS:
-        assert hasattr(engine_lib, name)
-    src = os.path.join(ROOT, "optimax_rogue_amd", "csrc", "orx_route.hip")
-    hdr = os.path.join(ROOT, "include", "orx_route.h")
-    assert (src, hdr) == (build.ROUTE_SRC, build.ROUTE_HDR)
-    h = hashlib.sha256()
-    for p in (src, hdr, build.QUERY_HDR, build.SEEK_HDR):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    assert build.route_id() == h.hexdigest()[:16] == _lib.route_build_id()
-    assert build.PARTS["route"] == build.Part("orx_route_build_id", "ORX_ROUTE_BUILD_ID",
-                                              (src, hdr, build.QUERY_HDR, build.SEEK_HDR), ())
-    assert src in build.EXTRA_SOURCES and src in build.SOURCES
-    ids = build.built_ids(_lib.LIB_PATH, every=True)
-    assert ids == build.tree_ids() and ids["route"] == build.route_id()
-    assert set(build.built_ids(_lib.LIB_PATH)) == {"engine", "path", "moves"}
 
 
 def test_route_header_in_a_plain_c_consumer(engine_lib, tmp_path):

@@ -14,7 +14,6 @@ checked exhaustively on small boards; then the row packing, the header against
 the export table and the library, the build id, and the host-side refusals
 from a plain C consumer.
 """
-import hashlib
 import os
 import re
 import subprocess
@@ -206,39 +205,10 @@ def test_header_is_the_export_table():
     assert int(re.search(r"#define ORX_SIGHT_SEEN (\d+)", text).group(1)) == sight.SIGHT_SEEN == 64
     decl = sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(orx_\w+)\s*\(", text, re.M)))
     assert decl == sorted(_lib.SIGHT_EXPORTS) == ["orx_sight", "orx_sight_build_id"]
-    assert not set(_lib.SIGHT_EXPORTS) & (
-        set(_lib.EXPORTS) | set(_lib.VIEW_EXPORTS) | set(_lib.PATH_EXPORTS)
-        | set(_lib.MOVES_EXPORTS) | set(_lib.NPC_EXPORTS) | set(_lib.NPC_QUERY_EXPORTS))
     for hdr in ("orx.h", "orx_view.h"):
         with open(os.path.join(ROOT, "include", hdr)) as f:
             assert "orx_sight" not in f.read()
     assert _lib.ABI_VERSION == 7
-
-
-def test_sight_symbols_and_build_id(engine_lib):
-    """The library exports the header's entry points; its sight id is the hash
-    of orx_sight.hip, orx_sight.h and orx_query.h and shows only under
-    ``every=True``."""
-    from optimax_rogue_amd import _lib, build
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
-                         text=True, check=True).stdout
-    assert set(_lib.SIGHT_EXPORTS) <= set(re.findall(r" T (orx_\w+)", out))
-    for name in _lib.SIGHT_EXPORTS:
-        assert hasattr(engine_lib, name)
-    src = os.path.join(ROOT, "optimax_rogue_amd", "csrc", "orx_sight.hip")
-    hdr = os.path.join(ROOT, "include", "orx_sight.h")
-    h = hashlib.sha256()
-    for p in (src, hdr, build.QUERY_HDR):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    assert build.sight_id() == h.hexdigest()[:16] == _lib.sight_build_id()
-    part = build.PARTS["sight"]
-    assert part == build.Part("orx_sight_build_id", "ORX_SIGHT_BUILD_ID",
-                              (src, hdr, build.QUERY_HDR), ())
-    assert src in build.EXTRA_SOURCES and src in build.SOURCES
-    ids = build.built_ids(_lib.LIB_PATH, every=True)
-    assert ids == build.tree_ids() and ids["sight"] == build.sight_id()
-    assert set(build.built_ids(_lib.LIB_PATH)) == {"engine", "path", "moves"}
 
 
 def test_sight_header_in_a_plain_c_consumer(engine_lib, tmp_path):

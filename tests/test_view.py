@@ -276,8 +276,8 @@ def test_engine_view_checks_come_before_the_library():
 
 def test_view_symbol_and_export_lists(engine_lib):
     """orx_view is exported by liborx.so and bound from a list of its own;
-    _lib.EXPORTS still equals what orx.h declares, and the build id hashes
-    the view's two files, the queries' shared header and the launch plan."""
+    _lib.EXPORTS still equals what orx.h declares (the engine's build id,
+    which hashes the view's two files too: tests/test_parts.py)."""
     from optimax_rogue_amd import _lib, build
     assert _lib.VIEW_EXPORTS == ("orx_view",)
     assert hasattr(engine_lib, "orx_view")
@@ -285,19 +285,11 @@ def test_view_symbol_and_export_lists(engine_lib):
                                               open(path).read(), re.M)))
     assert sorted(_lib.EXPORTS) == decl(os.path.join(ROOT, "include", "orx.h"))
     assert sorted(_lib.VIEW_EXPORTS) == decl(os.path.join(ROOT, "include", "orx_view.h"))
-    assert not set(_lib.EXPORTS) & set(_lib.VIEW_EXPORTS)
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
                          text=True, check=True).stdout
     assert "orx_view" in set(re.findall(r" T (orx_\w+)", out))
     assert re.search(r"#define ORX_ABI_VERSION 7\b", open(os.path.join(ROOT, "include",
                                                                       "orx.h")).read())
-    assert _lib.build_id() == build.source_id()
-    import hashlib
-    h = hashlib.sha256()
-    for p in (build.SRC, build.HDR, build.VIEW_SRC, build.VIEW_HDR, build.QUERY_HDR,
-              build.PLAN_HDR):
-        h.update(open(p, "rb").read())
-    assert build.source_id() == h.hexdigest()[:16]
     assert os.path.basename(build.PLAN_HDR) == "orx_plan.h"
     assert os.path.basename(build.QUERY_HDR) == "orx_query.h"
     assert os.path.basename(build.VIEW_SRC) == "orx_view.hip"

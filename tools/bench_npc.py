@@ -60,7 +60,7 @@ def main():
     B = int(opts.get("games", 65536))
     dev = torch.device("cuda", 0)
     ids = {"label": opts.get("label", "tree"), "build_id": _lib.build_id(),
-           "npc_build_id": _lib.npc_build_id(), "games": B, "n_npcs": K}
+           "npc_build_id": _lib.part_id("npc"), "games": B, "n_npcs": K}
     gen = torch.Generator().manual_seed(7)
     acts = torch.randint(1, 6, (RING, B), generator=gen, dtype=torch.int8).to(dev)
     tables = torch.randint(1, 6, (RING, K, B), generator=gen, dtype=torch.int8).to(dev)

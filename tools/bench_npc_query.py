@@ -70,8 +70,8 @@ def main():
     lib = _lib.load()
     has_query, has_given = hasattr(lib, "orx_npc_options"), hasattr(lib, "orx_npc_step")
     ids = {"label": opts.get("label", "tree"), "build_id": _lib.build_id(),
-           "moves_build_id": _lib.moves_build_id(), "path_build_id": _lib.path_build_id(),
-           "npc_query_build_id": _lib.npc_query_build_id(), "games": B, "n_npcs": K}
+           "moves_build_id": _lib.part_id("moves"), "path_build_id": _lib.part_id("path"),
+           "npc_query_build_id": _lib.part_id("npc_query"), "games": B, "n_npcs": K}
     gen = torch.Generator().manual_seed(7)
     lines = []
 
