@@ -21,6 +21,9 @@
  * may start or end on a staircase tile but cannot cross one.  orx_path_rows
  * computes that distance from arbitrary source cells (all of them: the pair
  * table of a bank); orx_path_seek reads the table for one player of every game.
+ * orx_path_threat reads it the other way round: how near what hunts a player
+ * is to its cell, to each move's cell and to every cell of a window -- the
+ * danger map -- and the move that flees.
  *
  * It is a header of its own so that orx.h's list of entry points stays what
  * it is; the conventions (caller-owned device pointers, asynchronous on the
@@ -158,6 +161,76 @@ int orx_path_rows(const orx_cfg_t* cfg, const uint8_t* bank_tiles,
 int orx_path_seek(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t* pairs,
                   int32_t player, int32_t* dist, int8_t* move, int16_t* target,
                   int64_t n_games, void* stream);
+
+/* ---- the danger field: how near the hunters are, and the move that flees ----
+ * The columns of orx_path_threat's rows (ORX_SEEK_COLS of them, seek's
+ * alignments; column 3 pads). */
+#define ORX_THREAT_PLAYER 0   /* column: the other player */
+#define ORX_THREAT_NPC    1   /* every NPC whose alive bit is set */
+#define ORX_THREAT_ANY    2   /* the union of both */
+#define ORX_THREAT_AFTER_COLS 8   /* a row of `after`: column m is Move m */
+
+/* For `player` (0 / 1) of every game, on that player's depth.  A THREAT of the
+ * player is the other player when it is on the viewer's depth, whatever its
+ * health, and every NPC slot of n_npcs whose alive bit is set when the viewer
+ * is on the NPCs' depth: exactly orx_path_seek's targets of its PLAYER and NPC
+ * columns (a viewer whose own cell is outside the grid has none).  Items are
+ * not threats.
+ *
+ * The VALUE of a cell c for a column, in the field's uint16 format:
+ *   ORX_PATH_WALL on a Wall tile or outside the W x H grid; else the unsigned
+ *   minimum, over the column's threats t, of the walking distance between t's
+ *   cell and c -- orx_path_seek's distance: pairs[p_layout[player]][t][c] with
+ *   a bank, the closed room form without one -- and ORX_PATH_UNREACHABLE where
+ *   no threat can walk to c (or the column has no threat).  The sentinels order
+ *   themselves under the unsigned minimum: WALL above UNREACHABLE above every
+ *   number of moves.  A threat whose cell is outside the grid reaches nothing.
+ * Outputs (each may be NULL, not all five):
+ *   dist   int32 [n_games][4], 16-byte aligned: the value of the player's own
+ *          cell; ORX_SEEK_UNREACHABLE where it is ORX_PATH_UNREACHABLE or above,
+ *          ORX_SEEK_ABSENT where the column has no threat (or the own cell is
+ *          outside the grid).
+ *   target int16 [n_games][4], 8-byte aligned: the nearest threat -- column
+ *          PLAYER: 1 - player; NPC: the lowest slot attaining dist; ANY: an
+ *          iden, 1 or 2 for a player and 3 + slot for an NPC, the player on a
+ *          tie; -1 when absent.
+ *   move   int8 [n_games][4], 4-byte aligned: the column's greedy flee move.
+ *          The candidates are ORX_MOVE_STAY with the own cell's value, then
+ *          ORX_MOVE_UP, RIGHT, DOWN, LEFT, each a candidate when its neighbour
+ *          cell is in the grid and its tile is Ground (a Wall is not, and
+ *          neither is a StaircaseDown: a step onto one descends -- that is
+ *          orx_path_query's move).  The largest value wins, UNREACHABLE above
+ *          every number; the first candidate in that order attaining it is
+ *          taken, so Stay wins every tie and a move is chosen only when it
+ *          strictly gains.  ORX_MOVE_STAY when absent.  Entities are not part
+ *          of the graph: a neighbour holding a threat has value 0 and never wins.
+ *   after  int32 [n_games][8], 16-byte aligned, for column ANY: column m is
+ *          Move m's candidate value in dist's convention (column ORX_MOVE_STAY
+ *          equals dist[ANY]); ORX_SEEK_ABSENT where the move is no candidate,
+ *          where there is no threat, and in columns 0, 6 and 7.
+ *   window uint16 [n_games][V][V], V = 2 * radius + 1, 1 <= radius <=
+ *          ORX_VIEW_MAX_RADIUS: column ANY's value of every cell in orx_view's
+ *          geometry (orx_path_query's window).  With no threat at all it holds
+ *          ORX_PATH_WALL on Wall and off-grid cells and ORX_PATH_UNREACHABLE
+ *          elsewhere.  When window is NULL, radius is ignored.
+ *   Column 3 of dist, target and move is ORX_SEEK_ABSENT, -1, ORX_MOVE_STAY.
+ * So: columns PLAYER and NPC of dist and target equal orx_path_seek's columns
+ * of the same name; where column ANY has a threat the window's centre is
+ * dist[ANY] (ORX_PATH_UNREACHABLE and above for ORX_SEEK_UNREACHABLE), and its
+ * four neighbours are after's values wherever those moves are candidates.
+ * Reads the state, writes only its outputs; no host sync (it can be captured
+ * in a graph behind orx_env_step), no random words; nothing depends on
+ * status.  ORX_EINVAL, on the host before any launch: player not 0 / 1, five
+ * NULL outputs, a bad radius with a window, a misaligned output (window: 2
+ * bytes), n_games <= 0, a configuration orx_validate_cfg refuses, a bank
+ * without pairs, p_layout or bank_tiles, a window without a bank on a grid
+ * whose largest distance (W - 3) + (H - 3) + 2 would reach the sentinels, or a
+ * NULL state pointer that is read (p_x, p_y, p_depth; st_x and st_y without a
+ * bank; npc_pos, npc_health and npc_alive with NPCs). */
+int orx_path_threat(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t* pairs,
+                    int32_t player, int32_t radius,
+                    int32_t* dist, int8_t* move, int16_t* target, int32_t* after,
+                    uint16_t* window, int64_t n_games, void* stream);
 
 /* The id of the sources this part of the library was built from: the first 16
  * hex digits of SHA-256(orx_path.hip || orx_path.h), as orx_build_id() is of

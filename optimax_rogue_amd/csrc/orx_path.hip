@@ -52,6 +52,17 @@
 // column = its own: the table is symmetric), keeps the least per column, and
 // reads the chosen target's row at its four neighbours for the move (the
 // Seeker of orx_seek.h, which orx_npc_seek shares).
+//
+// threat_kernel: seek_kernel's shape with the question turned round -- a lane
+// per game loops over the live threats and reads each one's row of the table
+// at five cells (its own, y -+ 1 beside it, x -+ 1 at -+ H entries: at most
+// three cache lines), keeping the least per cell for the other player and for
+// the NPCs; the union column is their cellwise minimum, the flee move the
+// first of Stay, Up, Right, Down, Left with the largest.
+// threat_window_kernel: window_kernel's staging and transpose; every tile cell
+// is owned by one lane through the loop over the game's threats, so the
+// minimum needs no atomics and no barrier.  The rows are threat_kernel's body
+// run by the first lanes after the tile has been streamed out.
 // Plain C++ and vector stores only.
 #include <cstdlib>
 
@@ -582,6 +593,269 @@ __global__ __launch_bounds__(kBlock) void seek_kernel(const SeekArgs a) {
         make_uint2(target[0] | target[1] << 16, target[2] | 0xFFFFu << 16);
 }
 
+// ---------------------------------------------------------------------------
+// threat: the danger field and the move that flees it
+// ---------------------------------------------------------------------------
+struct ThreatArgs {
+  const int32_t *p_x, *p_y, *p_depth, *st_x, *st_y;
+  const int16_t* p_layout;
+  const uint8_t* bank_tiles;
+  const uint16_t* npc_pos;
+  const uint32_t* npc_alive;
+  const uint16_t* pairs;
+  int32_t* dist;
+  int8_t* move;
+  int16_t* target;
+  int32_t* after;
+  uint16_t* window;
+  int64_t B;
+  int32_t W, H, K, L, player, npc_depth, R, G;
+  uint32_t inv_vv, inv_v;  // (R, G, inv_vv, inv_v: a Window, with `window`)
+};
+
+// whether cell (cx, cy), in the grid, is Ground: what a flee move may step on
+__device__ __forceinline__ bool ground(const Seeker& s, int cx, int cy) {
+  if (s.tiles) return (s.tiles[cx * s.H + cy] & ORX_VIEW_TILE_MASK) == ORX_TILE_GROUND;
+  return (uint32_t)(cx - 1) < (uint32_t)(s.W - 2) && (uint32_t)(cy - 1) < (uint32_t)(s.H - 2) &&
+         !(cx == s.sx && cy == s.sy);
+}
+
+// One column's value -- the least walking distance to its threats, kNoPath
+// where none reaches -- on the five cells a flee move chooses among: the own
+// cell, then Up, Right, Down, Left (only the candidates of `cand`, bit j: cell
+// j, are looked up); and the lowest slot attaining the own cell's.
+struct Around {
+  uint32_t v[5] = {kNoPath, kNoPath, kNoPath, kNoPath, kNoPath};
+  int32_t slot = -1;
+  __device__ __forceinline__ void offer(const Seeker& s, uint32_t cand, int32_t k, int tx, int ty) {
+    const int cx[5] = {s.x, s.x, s.x + 1, s.x, s.x - 1}, cy[5] = {s.y, s.y - 1, s.y, s.y + 1, s.y};
+    const bool in = s.inside(tx, ty);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const uint32_t d = in && ((cand >> j) & 1u) ? s.between(cx[j], cy[j], tx, ty) : kNoPath;
+      if (j == 0 && (slot < 0 || d < v[0])) slot = k;
+      v[j] = d < v[j] ? d : v[j];
+    }
+  }
+  // a value in dist's convention
+  __device__ __forceinline__ static uint32_t shown(uint32_t d) {
+    return (uint32_t)(d == kNoPath ? ORX_SEEK_UNREACHABLE : (int32_t)d);
+  }
+  // Stay, then the first candidate that strictly gains on the best so far
+  __device__ __forceinline__ uint32_t flee(uint32_t cand) const {
+    uint32_t best = v[0], m = ORX_MOVE_STAY;
+#pragma unroll
+    for (int j = 1; j < 5; ++j)
+      if (((cand >> j) & 1u) && v[j] > best) best = v[j], m = (uint32_t)(ORX_MOVE_UP + j - 1);
+    return m;
+  }
+};
+
+// game b's rows of dist, move, target and after: one lane, a loop over the
+// live threats with five lookups in each one's row of the pair table (the own
+// cell, y -+ 1 beside it, x -+ 1 at -+ H entries)
+__device__ __forceinline__ void threat_rows(const ThreatArgs& a, int64_t b) {
+  const int64_t B = a.B;
+  const int K = a.K;
+  const auto [me, ot] = player_rows(a.player, B, b);
+
+  Seeker s;
+  s.W = a.W, s.H = a.H;
+  s.x = a.p_x[me], s.y = a.p_y[me];
+  s.sx = s.sy = -1, s.table = nullptr, s.tiles = nullptr;
+  if (a.L > 0) {
+    const size_t lay = (size_t)layout_of(a, me), WH = (size_t)(a.W * a.H);
+    s.table = a.pairs + lay * WH * WH;
+    s.tiles = a.bank_tiles + lay * WH;
+  } else {
+    s.sx = a.st_x[me], s.sy = a.st_y[me];
+  }
+  const int32_t d = a.p_depth[me];
+  const bool here = s.inside(s.x, s.y);  // (a cell outside the grid has no threats)
+
+  // the candidates: the own cell, and the neighbours that are Ground
+  uint32_t cand = 1u;
+  if (here) {
+    const int nx[4] = {s.x, s.x + 1, s.x, s.x - 1}, ny[4] = {s.y - 1, s.y, s.y + 1, s.y};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (s.inside(nx[j], ny[j]) && ground(s, nx[j], ny[j])) cand |= 2u << j;
+  }
+
+  Around col[3];
+  if (here && a.p_depth[ot] == d)
+    col[ORX_THREAT_PLAYER].offer(s, cand, 1 - a.player, a.p_x[ot], a.p_y[ot]);
+  if (here && K > 0 && d == a.npc_depth) {
+    uint32_t alive = 0;
+    for (int k = 0; k < K; ++k) {
+      if ((k & 31) == 0) alive = a.npc_alive[(int64_t)(k >> 5) * B + b];
+      if (!((alive >> (k & 31)) & 1u)) continue;
+      const uint32_t pos = a.npc_pos[(int64_t)k * B + b];
+      col[ORX_THREAT_NPC].offer(s, cand, k, (int)(pos & 0xFFu), (int)(pos >> 8));
+    }
+  }
+  // the union: the cellwise minimum; the player wins a tie
+  const Around &p = col[ORX_THREAT_PLAYER], &n = col[ORX_THREAT_NPC];
+  Around& u = col[ORX_THREAT_ANY];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) u.v[j] = p.v[j] < n.v[j] ? p.v[j] : n.v[j];
+  u.slot = p.slot >= 0 && (n.slot < 0 || p.v[0] <= n.v[0]) ? 2 - a.player
+           : n.slot >= 0 ? 3 + n.slot : -1;
+
+  uint32_t dist[3], move[3], target[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const Around& c = col[j];
+    dist[j] = c.slot < 0 ? (uint32_t)ORX_SEEK_ABSENT : Around::shown(c.v[0]);
+    move[j] = c.slot < 0 ? (uint32_t)ORX_MOVE_STAY : c.flee(cand);
+    target[j] = (uint32_t)c.slot & 0xFFFFu;
+  }
+
+  // a game's row of each output: one store (after: two)
+  store_seek_rows(a.dist, a.move, b, dist[0], dist[1], dist[2], move[0], move[1], move[2]);
+  if (a.target)
+    reinterpret_cast<uint2*>(a.target)[b] =
+        make_uint2(target[0] | target[1] << 16, target[2] | 0xFFFFu << 16);
+  if (a.after) {
+    const uint32_t none = (uint32_t)ORX_SEEK_ABSENT;
+    uint32_t w[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+      w[j] = u.slot >= 0 && ((cand >> j) & 1u) ? Around::shown(u.v[j]) : none;
+    uint4* row = reinterpret_cast<uint4*>(a.after) + 2 * b;
+    row[0] = make_uint4(none, w[1], w[2], w[3]);  // (column m: Move m; Stay is 5)
+    row[1] = make_uint4(w[4], w[0], none, none);
+  }
+}
+
+// no window: one lane per game
+__global__ __launch_bounds__(kBlock) void threat_kernel(const ThreatArgs a) {
+  const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (b < a.B) threat_rows(a, b);
+}
+
+// header fields staged per game ([kThreatHdr][G] int32 in LDS)
+// (T_OTHER: whether the other player hunts; T_NPCS: the live NPCs that do, in the grid)
+enum { T_PX, T_PY, T_SX, T_SY, T_LAYOUT, T_OX, T_OY, T_OTHER, T_NPCS, kThreatHdr };
+
+// LDS of a workgroup of G games: the tile, the headers, and the cells of the
+// NPCs that hunt, uint16 [K][G] (x | y << 8, as npc_pos packs them)
+inline size_t threat_lds(int G, int VV, int K) {
+  return (size_t)G * VV * sizeof(uint16_t) + sizeof(int32_t) * G * kThreatHdr +
+         sizeof(uint16_t) * G * K;
+}
+
+// window_kernel's staging.  A game's lane also lists the cells of the NPCs
+// that hunt it in LDS (coalesced over the games, once per workgroup), so the
+// tile's loop reads threats from LDS alone.  Every tile cell is owned by one
+// lane for the whole loop over the game's threats -- it starts at Wall or
+// "unreachable" and takes the minimum of each threat's distance -- so the loop
+// has no atomics and no barrier.  A bank: 16 or 32 neighbouring lanes take a
+// window column, which is consecutive uint16 in a threat's row of the pair
+// table (window_kernel's transpose).  The room: a lane per cell, the closed
+// form per threat.  The rows of the other outputs are threat_rows' by the
+// first nb lanes, after the tile has left, so that the other waves retire
+// meanwhile.
+__global__ __launch_bounds__(kBlock) void threat_window_kernel(const ThreatArgs a) {
+  extern __shared__ uint4 smem[];
+  const Window win = Window::of(a.R, a.G, a.inv_vv, a.inv_v);
+  const int G = win.G, R = win.R, V = win.V, VV = win.VV, W = a.W, H = a.H, K = a.K;
+  uint16_t* tile = reinterpret_cast<uint16_t*>(smem);  // G * VV uint16 (G % 8 == 0: whole uint4s)
+  int32_t* hdr = reinterpret_cast<int32_t*>(tile + G * VV);
+  uint16_t* npcs = reinterpret_cast<uint16_t*>(hdr + kThreatHdr * G);  // [K][G]
+  const int64_t B = a.B;
+  const int64_t b0 = (int64_t)blockIdx.x * G;
+  const int nb = (int)((B - b0) < (int64_t)G ? (B - b0) : (int64_t)G);
+  const int t = threadIdx.x;
+
+  // 1. the games' headers and threats, coalesced over the games
+  if (t < nb) {
+    const int64_t b = b0 + t;
+    const auto [me, ot] = player_rows(a.player, B, b);
+    const int x = a.p_x[me], y = a.p_y[me], ox = a.p_x[ot], oy = a.p_y[ot];
+    const int32_t d = a.p_depth[me];
+    const bool here = (uint32_t)x < (uint32_t)W && (uint32_t)y < (uint32_t)H;
+    hdr[T_PX * G + t] = x;
+    hdr[T_PY * G + t] = y;
+    hdr[T_SX * G + t] = a.L > 0 ? 0 : a.st_x[me];
+    hdr[T_SY * G + t] = a.L > 0 ? 0 : a.st_y[me];
+    hdr[T_LAYOUT * G + t] = layout_of(a, me);
+    hdr[T_OX * G + t] = ox;
+    hdr[T_OY * G + t] = oy;
+    hdr[T_OTHER * G + t] = here && a.p_depth[ot] == d && (uint32_t)ox < (uint32_t)W &&
+                           (uint32_t)oy < (uint32_t)H;
+    int n = 0;
+    if (here && K > 0 && d == a.npc_depth) {
+      uint32_t alive = 0;
+      for (int k = 0; k < K; ++k) {
+        if ((k & 31) == 0) alive = a.npc_alive[(int64_t)(k >> 5) * B + b];
+        if (!((alive >> (k & 31)) & 1u)) continue;
+        const uint32_t pos = a.npc_pos[(int64_t)k * B + b];
+        if ((int)(pos & 0xFFu) < W && (int)(pos >> 8) < H) npcs[n++ * G + t] = (uint16_t)pos;
+      }
+    }
+    hdr[T_NPCS * G + t] = n;
+  }
+  __syncthreads();
+
+  // 2. the tile.  least(g, val, at): the least of at(tx, ty) over game g's
+  // threats and of `val`
+  auto least = [&](int g, uint32_t val, auto at) {
+    if (hdr[T_OTHER * G + g]) {
+      const uint32_t v = at(hdr[T_OX * G + g], hdr[T_OY * G + g]);
+      val = v < val ? v : val;
+    }
+    const int n = hdr[T_NPCS * G + g];
+    for (int k = 0; k < n; ++k) {
+      const uint32_t pos = npcs[k * G + g];
+      const uint32_t v = at((int)(pos & 0xFFu), (int)(pos >> 8));
+      val = v < val ? v : val;
+    }
+    return val;
+  };
+  if (a.L == 0) {
+    const int cells = nb * VV;
+    for (int c = t; c < cells; c += kBlock) {
+      const Window::Cell at = win.split((uint32_t)c);
+      const int g = at.g, x = hdr[T_PX * G + g] + at.i - R, y = hdr[T_PY * G + g] + at.j - R;
+      uint32_t val = kWall;
+      if ((uint32_t)(x - 1) < (uint32_t)(W - 2) && (uint32_t)(y - 1) < (uint32_t)(H - 2)) {
+        const int sx = hdr[T_SX * G + g], sy = hdr[T_SY * G + g];
+        val = least(g, kFar, [&](int tx, int ty) { return room<kFar>(W, H, sx, sy, x, y, tx, ty); });
+      }
+      tile[c] = (uint16_t)val;
+    }
+  } else {
+    const int cols = nb * V;
+    const size_t WH = (size_t)(W * H);
+    const int shift = V <= 16 ? 4 : 5, j = t & ((1 << shift) - 1);
+    if (j < V) {
+      for (int col = t >> shift; col < cols; col += kBlock >> shift) {
+        const int g = win.div_v((uint32_t)col), i = col - g * V;
+        const int x = hdr[T_PX * G + g] + i - R, y = hdr[T_PY * G + g] + j - R;
+        uint32_t val = kWall;
+        if ((uint32_t)x < (uint32_t)W && (uint32_t)y < (uint32_t)H) {
+          const size_t lay = (size_t)hdr[T_LAYOUT * G + g], c = (size_t)(x * H + y);
+          // (a game without a threat still shows its Walls)
+          val = (a.bank_tiles[lay * WH + c] & ORX_VIEW_TILE_MASK) == ORX_TILE_WALL ? kWall : kFar;
+          const uint16_t* column = a.pairs + lay * WH * WH + c;  // cell c of every row
+          val = least(g, val, [&](int tx, int ty) -> uint32_t {
+            return column[(size_t)(tx * H + ty) * WH];
+          });
+        }
+        tile[g * VV + j * V + i] = (uint16_t)val;
+      }
+    }
+  }
+  __syncthreads();
+
+  // 3. the tile's nb * VV contiguous cells to HBM
+  stream_out(tile, a.window + (size_t)b0 * (size_t)VV, nb * VV, t);
+
+  // 4. the other outputs' rows
+  if (t < nb && (a.dist || a.move || a.target || a.after)) threat_rows(a, b0 + t);
+}
+
 }  // namespace orx_path_dev
 
 #ifndef ORX_PATH_BUILD_ID
@@ -737,4 +1011,61 @@ extern "C" int orx_path_seek(const orx_cfg_t* cfg, const orx_state_t* st, const 
   const unsigned grid = (unsigned)((n_games + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(seek_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
   return orx_dev::launch_status("orx_path_seek");
+}
+
+extern "C" int orx_path_threat(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t* pairs,
+                               int32_t player, int32_t radius, int32_t* dist, int8_t* move,
+                               int16_t* target, int32_t* after, uint16_t* window, int64_t n_games,
+                               void* stream) {
+  using namespace orx_path_dev;
+  using orx_dev::fail;
+  int r;
+  if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_path_threat", player))) return r;
+  if (!dist && !move && !target && !after && !window)
+    return fail(ORX_EINVAL, "orx_path_threat: dist, move, target, after and window are all NULL");
+  if (window && (radius < 1 || radius > ORX_VIEW_MAX_RADIUS))
+    return fail(ORX_EINVAL, "orx_path_threat: radius must be in [1, ORX_VIEW_MAX_RADIUS]");
+  if ((r = check_games("orx_path_threat", n_games))) return r;
+  // (a row is one vector store, after's two)
+  if (misaligned(dist, 16) || misaligned(move, 4) || misaligned(target, 8) ||
+      misaligned(after, 16) || misaligned(window, 2))
+    return fail(ORX_EINVAL,
+                "orx_path_threat: dist and after must be 16-byte, move 4-byte, target 8-byte and "
+                "window 2-byte aligned");
+  if ((r = check_state(cfg, st, kStairsNoBank | kBank | kNpcs))) return r;
+  if (!st->p_depth) return fail(ORX_EINVAL, "a required state pointer is NULL");
+  if (cfg->n_layouts > 0) {
+    if (!pairs) return fail(ORX_EINVAL, "orx_path_threat: n_layouts > 0 needs pairs");
+  } else if (window && (int64_t)cfg->width + cfg->height - 4 >= (int64_t)ORX_PATH_UNREACHABLE) {
+    // the closed form's largest value, (W - 3) + (H - 3) + 2, must stay below the sentinels
+    return fail(ORX_EINVAL, "orx_path_threat: W + H too large for a window of uint16 distances");
+  }
+
+  ThreatArgs a;
+  a.p_x = st->p_x, a.p_y = st->p_y, a.p_depth = st->p_depth;
+  a.st_x = st->st_x, a.st_y = st->st_y;
+  a.p_layout = st->p_layout, a.bank_tiles = st->bank_tiles;
+  a.npc_pos = st->npc_pos, a.npc_alive = st->npc_alive;
+  a.pairs = cfg->n_layouts > 0 ? pairs : nullptr;
+  a.dist = dist, a.move = move, a.target = target, a.after = after, a.window = window;
+  a.B = n_games;
+  a.W = cfg->width, a.H = cfg->height, a.K = cfg->n_npcs, a.L = cfg->n_layouts;
+  a.player = player;
+  a.npc_depth = npc_depth(cfg);
+  if (!window) {
+    a.R = 0, a.G = 0, a.inv_vv = a.inv_v = 0;
+    const unsigned grid = (unsigned)((n_games + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(threat_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
+    return orx_dev::launch_status("orx_path_threat");
+  }
+  // (fewer games where the NPCs' cells would not fit beside the tile: 16 always do)
+  Window win = Window::fit(radius, sizeof(uint16_t));
+  while (win.G > 16 && threat_lds(win.G, win.VV, a.K) > (size_t)kDefaultLds)
+    win = Window::fit(radius, sizeof(uint16_t), win.G >> 1);
+  const int G = win.G;
+  a.R = win.R, a.G = G, a.inv_vv = win.inv_vv, a.inv_v = win.inv_v;
+  const size_t lds = threat_lds(G, win.VV, a.K);
+  const unsigned grid = (unsigned)((n_games + G - 1) / G);
+  hipLaunchKernelGGL(threat_window_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, a);
+  return orx_dev::launch_status("orx_path_threat");
 }

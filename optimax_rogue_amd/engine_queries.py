@@ -415,6 +415,83 @@ class EngineQueries:
                    _ptr(outs[2]), self.B, self._stream())
         return tuple(outs)
 
+    def threat(self, player: int = 0, radius: Optional[int] = None, out=None):
+        """orx_path_threat (include/orx_path.h): the danger field of ``player``
+        (0 / 1) of every game -- how many moves away what hunts it is along
+        walkable cells of its depth, and the move that flees.  A threat is the
+        other player and every live NPC (``seek``'s SEEK_PLAYER and SEEK_NPC
+        targets).  Returns ``(dist, move, target, after)``: int32, int8 and
+        int16 [n_games, SEEK_COLS = 4], columns THREAT_PLAYER, THREAT_NPC,
+        THREAT_ANY (the union) and one of padding, and int32 [n_games,
+        THREAT_AFTER_COLS = 8].  ``dist`` is the least distance from a threat
+        of the column (SEEK_UNREACHABLE / SEEK_ABSENT as in ``seek``),
+        ``target`` the nearest one (THREAT_ANY: an iden), ``move`` the first of
+        Stay, Up, Right, Down, Left -- a move only onto Ground -- after which
+        that distance is largest (Stay on every tie), and column ``m`` of
+        ``after`` what Move ``m`` would leave of ``dist[:, THREAT_ANY]``
+        (SEEK_ABSENT: not a candidate), a mask or a shaping term for a policy's
+        logits.  With a ``radius`` (1..15) also ``window``, uint16 [n_games, V,
+        V]: THREAT_ANY's value of every cell in ``view``'s geometry, the
+        danger map (PATH_WALL on walls and outside the grid, PATH_UNREACHABLE
+        where nothing hunts).  One launch on the current stream from the
+        resident state, no host sync, no state change, no random words; with a
+        bank the first call also builds ``pair_field``.  ``out``: a tuple of
+        the four (five with a radius) tensors written and returned instead of
+        fresh ones.  The host reference is ``path.threat(self.snapshot(),
+        ...)``."""
+        from .path import SEEK_COLS, THREAT_AFTER_COLS
+        from .query import check_player, check_radius
+        check_player(player)
+        if radius is not None:
+            check_radius(radius)
+        self._require("orx_path_threat")
+        row = (self.B, SEEK_COLS)
+        specs = [(torch.int32, row), (torch.int8, row), (torch.int16, row),
+                 (torch.int32, (self.B, THREAT_AFTER_COLS))]
+        names = ("dist", "move", "target", "after")
+        if radius is not None:
+            V = 2 * int(radius) + 1
+            specs.append((torch.uint16, (self.B, V, V)))
+            names += ("window",)
+        outs = self._outs(out, specs, "(dist, move, target, after), or (dist, move, target, "
+                          "after, window) with a radius", distinct=names)
+        # (a row is one vector store, after's two; the window may start at any uint16)
+        if any(t.data_ptr() % 16 for t in outs[:4]):
+            raise ValueError("out: dist, move, target and after must be 16-byte aligned")
+        pairs = self.pair_field
+        self._call("orx_path_threat", _ptr(pairs), int(player), int(radius or 0), *map(_ptr, outs),
+                   *([None] if radius is None else []), self.B, self._stream())
+        return tuple(outs)
+
+    def threat_view(self, radius: int, player: int = 0) -> torch.Tensor:
+        """``threat(player, radius)``'s window alone, uint16 [n_games, V, V]:
+        orx_path_threat with its other outputs NULL (the danger map as an
+        observation plane beside ``view``)."""
+        from .query import check_player, check_radius
+        check_player(player)
+        check_radius(radius)
+        self._require("orx_path_threat")
+        V = 2 * int(radius) + 1
+        window = torch.empty((self.B, V, V), dtype=torch.uint16, device=self.device)
+        self._call("orx_path_threat", _ptr(self.pair_field), int(player), int(radius), None, None,
+                   None, None, _ptr(window), self.B, self._stream())
+        return window
+
+    def flee_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games], ready as ``actions``: ``threat``'s move of column
+        THREAT_ANY alone (orx_path_threat with its other outputs NULL) -- the
+        step that puts the most walking distance between ``player`` and the
+        nearest of what hunts it; Stay where no step gains, where nothing hunts
+        and in a dead end (``path.flee_moves``)."""
+        from .path import SEEK_COLS, THREAT_ANY
+        from .query import check_player
+        check_player(player)
+        self._require("orx_path_threat")
+        move = torch.empty((self.B, SEEK_COLS), dtype=torch.int8, device=self.device)
+        self._call("orx_path_threat", _ptr(self.pair_field), int(player), 0, None, _ptr(move), None,
+                   None, None, self.B, self._stream())
+        return move[:, THREAT_ANY]
+
     def moves(self, player: int = 0, out=None):
         """orx_moves (include/orx_moves.h): what each move of ``player`` (0 / 1)
         would do in every game, as ``(kind, target, amount)``: uint8, int16 and

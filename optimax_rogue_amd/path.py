@@ -26,6 +26,11 @@ cells, and from a player to the other player, the nearest NPC and the nearest
 item.  The updater descends an entity that steps onto a free StaircaseDown
 (updater.py:205-206), so a walk that stays on its depth may start or end on a
 staircase but not cross one: the interior cells of a path are all Ground.
+
+``threat`` (``orx_path_threat``) turns ``seek`` round: the least of those
+distances from what hunts a player -- the other player, the live NPCs -- to its
+own cell, to each move's cell and to every cell of a window, and the move after
+which it is largest (``flee_moves``).
 """
 from __future__ import annotations
 
@@ -41,6 +46,9 @@ PATH_UNREACHABLE = 0xFFFE
 SEEK_PLAYER, SEEK_NPC, SEEK_ITEM, SEEK_COLS = 0, 1, 2, 4
 SEEK_UNREACHABLE = -1
 SEEK_ABSENT = -2
+# include/orx_path.h ORX_THREAT_*
+THREAT_PLAYER, THREAT_NPC, THREAT_ANY = 0, 1, 2
+THREAT_AFTER_COLS = 8
 
 
 def check_path_args(player: int, radius=None, cfg=None) -> None:
@@ -347,3 +355,113 @@ def seek(snap: dict, cfg, player: int, bank=None):
         fill_column(out, col, own != PATH_WALL, own, walk.first_move(px, py, bx, by, own),
                     slots[best])
     return out
+
+
+# -- the danger field (orx_path_threat) ----------------------------------------
+def _least(walk: Walk, x, y, present, tx, ty):
+    """int64, the shape of cells (x, y) [B, ...]: the least walking distance to
+    the threats ``present`` [T, B] at (tx, ty) [T, B], PATH_UNREACHABLE where
+    none reaches the cell (or there is none).  A Wall or off-grid cell is the
+    caller's to mark."""
+    out = np.full(np.broadcast(x, y).shape, PATH_UNREACHABLE, np.int64)
+    for k in np.flatnonzero(present.any(axis=1)):
+        v = np.minimum(walk.between(x, y, per_game(tx[k], x), per_game(ty[k], x)), PATH_UNREACHABLE)
+        out = np.where(per_game(present[k], x), np.minimum(out, v), out)
+    return out
+
+
+def threat(snap: dict, cfg, player: int, radius=None, bank=None):
+    """``(dist, move, target, after, window)`` of ``player`` (0 / 1) of every
+    game of a ``snapshot()``-shaped dict: the danger field, the flip side of
+    ``seek``.  A threat is the other player (on the viewer's depth) and every
+    NPC whose alive bit is set (when the viewer is on the NPCs' depth): the
+    targets of ``seek``'s SEEK_PLAYER and SEEK_NPC columns.  The value of a
+    cell for a column is the least walking distance (``seek``'s) from a threat
+    of the column to it, in the field's format: PATH_WALL on a Wall or outside
+    the grid, PATH_UNREACHABLE where no threat can walk to it.
+
+    dist    int32 [B, SEEK_COLS], columns THREAT_PLAYER, THREAT_NPC, THREAT_ANY
+            (the union) and one of padding: the value of the own cell,
+            SEEK_UNREACHABLE from PATH_UNREACHABLE up, SEEK_ABSENT without a
+            threat
+    move    int8 [B, SEEK_COLS]: the greedy flee move -- of Stay, then Up,
+            Right, Down, Left where the neighbour cell is Ground (not a Wall,
+            not a staircase), the first with the largest value, so a move is
+            taken only when it strictly gains; Stay when absent
+    target  int16 [B, SEEK_COLS]: the nearest threat -- ``1 - player``, the
+            lowest NPC slot attaining ``dist``, and for THREAT_ANY an iden (1 /
+            2 a player, 3 + slot an NPC; the player on a tie); -1 when absent
+    after   int32 [B, THREAT_AFTER_COLS]: column ``m`` is Move ``m``'s value for
+            THREAT_ANY in ``dist``'s convention (column Stay is ``dist[:,
+            THREAT_ANY]``), SEEK_ABSENT where the move is no candidate or there
+            is no threat
+    window  with a ``radius``, uint16 [B, V, V]: THREAT_ANY's value of every
+            cell in ``render_view``'s geometry; else None"""
+    check_player(player)
+    if radius is not None:
+        check_radius(radius)
+    p, q = int(player), 1 - int(player)
+    K = int(cfg.n_npcs)
+    bank = bank_of(cfg, bank)
+    walk = Walk(cfg, snap, p, bank)
+    layouts = None if bank is None else bank.layouts
+    px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
+    B = len(px)
+    depth = i64(snap["p_depth"][p])
+    here = inside_grid(cfg, px, py)
+    # the threats, [T, B]: the other player, then the NPC slots
+    present = [(here & (i64(snap["p_depth"][q]) == depth))[None]]
+    tx, ty = [i64(snap["p_x"][q])[None]], [i64(snap["p_y"][q])[None]]
+    if K > 0:
+        alive, nx, ny, _ = npc_rows(snap, K)
+        present.append(alive & (here & (depth == npc_depth(cfg))))
+        tx.append(nx)
+        ty.append(ny)
+    present, tx, ty = (np.concatenate(a) for a in (present, tx, ty))
+    columns = {THREAT_PLAYER: slice(0, 1), THREAT_NPC: slice(1, 1 + K)}
+
+    # the five cells a move chooses among: the own cell, then Up, Right, Down, Left
+    cx = np.stack([px] + [px + dx for _, dx, _ in MOVE_DELTAS], axis=1)          # [B, 5]
+    cy = np.stack([py] + [py + dy for _, _, dy in MOVE_DELTAS], axis=1)
+    inside, tile = tile_at(cfg, snap, p, cx, cy, layouts)
+    cand = inside & (tile == int(Tile.Ground))
+    cand[:, 0] = True
+
+    out = seek_columns((B,), np.int16)
+    vals, has, slot = {}, {}, {}
+    for col, sl in columns.items():
+        pr = present[sl]
+        vals[col] = _least(walk, cx, cy, pr, tx[sl], ty[sl])
+        has[col] = pr.any(axis=0)
+        # the lowest slot attaining the own cell's value (absent above unreachable)
+        own = np.minimum(walk.between(px[:, None], py[:, None], tx[sl].T, ty[sl].T),
+                         PATH_UNREACHABLE)
+        slot[col] = np.where(pr.T, own, PATH_WALL).argmin(axis=1) if pr.shape[0] else np.zeros(B, int)
+    P, N, A = THREAT_PLAYER, THREAT_NPC, THREAT_ANY
+    vals[A], has[A] = np.minimum(vals[P], vals[N]), has[P] | has[N]
+    player_first = has[P] & (~has[N] | (vals[P][:, 0] <= vals[N][:, 0]))
+    chosen = {P: np.full(B, q), N: slot[N], A: np.where(player_first, 1 + q, 3 + slot[N])}
+    for col in (P, N, A):
+        best, move = vals[col][:, 0], np.full(B, int(Move.Stay))
+        for j, (code, _, _) in enumerate(MOVE_DELTAS, start=1):
+            gains = cand[:, j] & (vals[col][:, j] > best)
+            move, best = np.where(gains, code, move), np.where(gains, vals[col][:, j], best)
+        fill_column(out, col, has[col], vals[col][:, 0], move, chosen[col])
+    dist, move, target = out
+    after = np.full((B, THREAT_AFTER_COLS), SEEK_ABSENT, np.int32)
+    shown = np.where(vals[A] >= PATH_UNREACHABLE, SEEK_UNREACHABLE, vals[A])
+    for j, code in enumerate([int(Move.Stay)] + [c for c, _, _ in MOVE_DELTAS]):
+        after[:, code] = np.where(has[A] & cand[:, j], shown[:, j], SEEK_ABSENT)
+    if radius is None:
+        return dist, move, target, after, None
+    wx, wy = window_cells(px, py, int(radius))
+    inside, tile = tile_at(cfg, snap, p, wx, wy, layouts)
+    window = np.where(inside & (tile != int(Tile.Wall)), _least(walk, wx, wy, present, tx, ty),
+                      PATH_WALL)
+    return dist, move, target, after, window.astype(np.uint16)
+
+
+def flee_moves(move) -> np.ndarray:
+    """int8 [B]: column THREAT_ANY of ``threat``'s ``move`` -- the step that
+    puts the most walking distance between the player and what hunts it."""
+    return np.asarray(move)[:, THREAT_ANY].astype(np.int8)

@@ -259,6 +259,33 @@ class VecEnv:
         dist, move, _ = self.engine.seek(player=player)
         return torch.where(dist[:, 0] > 0, move[:, 0], self.stair_moves(player))
 
+    def threat(self, player: int = 0, radius: Optional[int] = None, out=None):
+        """``(dist, move, target, after)`` of ``player`` (0: the learner) of
+        every game, and with a ``radius`` also the uint16 danger ``window``:
+        how many moves away the other player, the nearest NPC and the nearer
+        of the two (column THREAT_ANY) are along walkable cells, the move
+        after which that distance is largest, and what each move would leave
+        of it (``BatchedEngine.threat``; one launch, no host sync).  ``after``
+        shapes or masks a policy's logits as ``action_mask()`` does; ``dist[:,
+        THREAT_ANY]`` is the potential of a reward for keeping away."""
+        return self.engine.threat(player=player, radius=radius, out=out)
+
+    def threat_view(self, radius: int, player: int = 0) -> torch.Tensor:
+        """uint16 [n_games, 2 * radius + 1, 2 * radius + 1]: the danger map in
+        ``view``'s geometry -- every cell's walking distance from the nearest
+        of what hunts ``player`` (PATH_WALL on walls and outside the grid,
+        PATH_UNREACHABLE where nothing can come) -- ``threat``'s window alone
+        (``BatchedEngine.threat_view``; one launch, no host sync)."""
+        return self.engine.threat_view(radius, player=player)
+
+    def flee_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games]: the move that takes ``player`` one step away from
+        the nearest of what hunts it -- the other player and the live NPCs --
+        where a step onto Ground strictly gains walking distance, else Stay:
+        the counterpart of ``hunt_moves``, ready as ``actions`` for ``step``
+        or as self-play's second column (``BatchedEngine.flee_moves``)."""
+        return self.engine.flee_moves(player=player)
+
     # the enemies' side (include/orx_npc_query.h): what a policy for the NPCs
     # needs before it fills ``step``'s ``npc_moves``
     def npc_options(self, out=None):
