@@ -9,6 +9,10 @@
 //   step_n   W H K flags n_layouts rng npc_policy  B rows concurrency [VAR=value ...]
 //   env_step W H K flags n_layouts rng npc_policy  B obs_aligned [VAR=value ...]
 //
+// A line may begin with two more words, the device's SIMD count and its LDS
+// bytes per workgroup ("64 65536 rollout ..."): the plan on that device
+// (tests/test_instance_sweep.py shows its requests' plans do not depend on it).
+//
 // The VAR=value words are the line's ORX_* environment.  Output per line:
 //   form pm lanes nt threads blocks lds_bytes lds_n lds_bits lds_rows
 #include <cstdio>
@@ -22,14 +26,23 @@
 using namespace orx_dev;
 
 int main() {
-  const Device dev{1024, 160 * 1024};
+  const Device default_dev{1024, 160 * 1024};
   const char* forms[] = {"moving", "mt", "paired", "one-lane", "replay", "generic"};
   std::string line;
   while (std::getline(std::cin, line)) {
     std::istringstream in(line);
     std::string kind;
     orx_cfg_t c{};
-    if (!(in >> kind >> c.width >> c.height >> c.n_npcs >> c.flags >> c.n_layouts >> c.rng >>
+    Device dev = default_dev;
+    if (!(in >> kind)) continue;
+    if (kind[0] >= '0' && kind[0] <= '9') {  // the optional device: SIMDs, LDS bytes
+      dev.simds = atoi(kind.c_str());
+      if (!(in >> dev.lds_per_block >> kind) || dev.simds < 1) {
+        fprintf(stderr, "bad device: %s\n", line.c_str());
+        return 2;
+      }
+    }
+    if (!(in >> c.width >> c.height >> c.n_npcs >> c.flags >> c.n_layouts >> c.rng >>
           c.npc_policy))
       continue;
     long long a[6] = {0, 0, 0, 0, 0, 0};
