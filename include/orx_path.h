@@ -25,6 +25,12 @@
  * is to its cell, to each move's cell and to every cell of a window -- the
  * danger map -- and the move that flees.
  *
+ * All of these treat the enemies as air.  orx_path_ticks does not: a step onto
+ * an NPC's cell is an attack that leaves the mover where it is, so the ticks
+ * to the staircase are a shortest path with small integer entry costs over
+ * the positions and health of each game's NPCs -- a per-game search on the
+ * device, which no table over the bank can hold.
+ *
  * It is a header of its own so that orx.h's list of entry points stays what
  * it is; the conventions (caller-owned device pointers, asynchronous on the
  * caller's stream, ORX_OK or a negative code with orx_last_error) are orx.h's.
@@ -231,6 +237,76 @@ int orx_path_threat(const orx_cfg_t* cfg, const orx_state_t* st, const uint16_t*
                     int32_t player, int32_t radius,
                     int32_t* dist, int8_t* move, int16_t* target, int32_t* after,
                     uint16_t* window, int64_t n_games, void* stream);
+
+/* ---- ticks to the staircase through the enemies ------------------------------
+ * orx_path_query treats the enemies as air, but a step onto an NPC's cell is an
+ * attack (handle_move, updater.py:218-227): the mover stays where it is, the
+ * NPC loses the attacker's damage - armor (updater.py:313) and is swept at the
+ * end of the tick in which its health reaches 0 (updater.py:136-145); the step
+ * after that is free.  For `player` (0 / 1) of every game, on that player's
+ * depth d, this is the staircase distance with that term: the least number of
+ * ticks in which the player descends, fighting through or walking round.
+ *
+ * The GRAPH.  Cells are the in-grid tiles that are not Wall (Ground or
+ * StaircaseDown): with a bank planes[p_layout[player]], what orx_route_planes
+ * (orx_route.h) wrote for the state's bank_tiles, the layout index clamped as
+ * everywhere; without one EmptyDungeonGenerator's closed form (planes is NULL
+ * and ignored).  A live NPC HOLDS a cell when d is the NPCs' depth, the slot's
+ * alive bit is set and its npc_pos is in the grid.  Let a = max(damage -
+ * player_armor, 0), with damage as orx_moves has it without the mana term:
+ * p_rpg[ORX_RPG_DAMAGE] under any ORX_EXT_CHARACTER flag, cfg->player_damage
+ * otherwise.  hits(c) is ceil(max(health, 1) / a) for a held cell when a > 0
+ * (the least over the slots, should several hold one cell: the engine never
+ * places two); a held cell cannot be entered when a == 0; hits(c) is 0 for
+ * every other cell.  enter(c) = 1 + hits(c).  The other player and items are
+ * not part of the graph, exactly as in orx_path_query.
+ *
+ * The COST.  T(c), the value of a cell, is the least total of enter over a
+ * walk from c to any StaircaseDown tile: the sum of enter over every cell
+ * stepped onto, the staircase included.  The walk's interior cells are all
+ * Ground (a step onto a staircase descends, so a walk never crosses one).  T
+ * is 0 on a StaircaseDown tile, whoever stands on it, and T(c) does not
+ * include entering c itself.
+ *
+ * Outputs (each may be NULL, not all three):
+ *   ticks  int32 [n_games], 4-byte aligned: T of the own cell; -1 where there
+ *          is no such walk, or the own cell is a Wall or outside the grid.
+ *   move   int8 [n_games]: the first of ORX_MOVE_UP, RIGHT, DOWN, LEFT whose
+ *          neighbour n has enter(n) + T(n) == ticks; ORX_MOVE_STAY when ticks
+ *          <= 0.
+ *   window uint16 [n_games][V][V], 2-byte aligned, in orx_view's geometry and
+ *          orx_path_query's format: ORX_PATH_WALL on Wall and off-grid cells,
+ *          ORX_PATH_UNREACHABLE where T is infinite, T elsewhere.  When window
+ *          is NULL, radius is ignored.
+ *
+ * What it is EXACT for.  With no ORX_EXT_CHARACTER flag set, every NPC staying
+ * where it is (the reference's decide_npc_move, the default) and the other
+ * player on another depth or off the cells used, playing `move` every tick
+ * lowers ticks by exactly one per tick, and the player descends in the tick
+ * where it was 1.  Under ORX_EXT_MANA or ORX_EXT_ITEMS it is an UPPER BOUND
+ * under the same conditions (mana only adds damage, and so does a damage item
+ * picked up on the way); ORX_EXT_LEVELING leaves hits as they are.  Against
+ * NPCs that move it is an ESTIMATE.  Without a live NPC on the depth, ticks
+ * and move equal orx_path_query's dist and move; always ticks >= dist, and
+ * ticks == -1 with dist >= 0 happens only when a == 0.
+ *
+ * One launch, a wave per game, a per-game search in LDS (three bit planes of
+ * H * ceil(W / 32) words and the window's tile).  Reads the state, writes only
+ * its outputs; no host sync (it can be captured in a graph behind
+ * orx_env_step), no random words; nothing depends on status.  ORX_EINVAL, on
+ * the host before any launch: player not 0 / 1, three NULL outputs, a bad
+ * radius with a window, a misaligned output or misaligned planes (4 bytes),
+ * n_games <= 0, a configuration orx_validate_cfg refuses, width * height >
+ * 65536, a bank without planes, p_layout or bank_tiles, a window when width *
+ * height + 127 * n_npcs >= 0xFFFE (a value could reach the sentinels), or a
+ * NULL state pointer that is read (p_x, p_y, p_depth; st_x and st_y without a
+ * bank; npc_pos, npc_health and npc_alive with NPCs; p_rpg under a character
+ * flag).  ORX_EIO where the device refuses the LDS (a grid narrower than 64
+ * and thousands of rows tall). */
+int orx_path_ticks(const orx_cfg_t* cfg, const orx_state_t* st, const uint32_t* planes,
+                   int32_t player, int32_t radius,
+                   int32_t* ticks, int8_t* move, uint16_t* window,
+                   int64_t n_games, void* stream);
 
 /* The id of the sources this part of the library was built from: the first 16
  * hex digits of SHA-256(orx_path.hip || orx_path.h), as orx_build_id() is of

@@ -100,6 +100,7 @@ TABLES = {
         "orx_path_rows": (_int, [_cfg, vp, vp, vp, vp, i64, vp]),
         "orx_path_seek": (_int, [_cfg, _st, vp, i32, vp, vp, vp, i64, vp]),
         "orx_path_threat": (_int, [_cfg, _st, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+        "orx_path_ticks": (_int, [_cfg, _st, vp, i32, i32, vp, vp, vp, i64, vp]),
     },
     "orx_moves.h": {
         "orx_moves": (_int, [_cfg, _st, i32, vp, vp, vp, i64, vp]),

@@ -63,6 +63,13 @@
 // is owned by one lane through the loop over the game's threats, so the
 // minimum needs no atomics and no barrier.  The rows are threat_kernel's body
 // run by the first lanes after the tile has been streamed out.
+//
+// ticks_kernel: route_kernel's shape -- a wave per game, bit planes in LDS, no
+// workgroup barrier -- for the one query here that no table can answer: a
+// Dijkstra backwards from the staircases in steps of game time, in which the
+// cells NPCs hold keep the wave back for the blows they cost (the comment at
+// the kernel has the rest).  Its step and the room's words are orx_seek.h's,
+// shared with orx_route.hip.
 // Plain C++ and vector stores only.
 #include <cstdlib>
 
@@ -856,6 +863,263 @@ __global__ __launch_bounds__(kBlock) void threat_window_kernel(const ThreatArgs 
   if (t < nb && (a.dist || a.move || a.target || a.after)) threat_rows(a, b0 + t);
 }
 
+// ---------------------------------------------------------------------------
+// ticks: the staircase distance through the enemies
+// ---------------------------------------------------------------------------
+constexpr int kTicksPlanes = 3;           // open, and the emitting set twice
+constexpr int kSlotPasses = 4;            // NPC slots a lane owns at most: slot k is lane k % 64's
+constexpr uint32_t kWaiting = 0xFFFFFFFFu;  // a slot whose cell the wave has not met
+constexpr uint32_t kNever = 0xFFFFFFFEu;    // a slot with nothing (more) to release
+
+struct TicksArgs {
+  const int32_t *p_x, *p_y, *p_depth, *st_x, *st_y, *p_rpg;
+  const int16_t* p_layout;
+  const uint16_t* npc_pos;
+  const int8_t* npc_health;
+  const uint32_t* npc_alive;
+  const uint32_t* planes;
+  int32_t* ticks;
+  int8_t* move;
+  uint16_t* window;
+  int64_t B;
+  int32_t W, H, WW, L, K, player, npc_depth, G, R;
+  int32_t damage, armor, character;  // cfg's; character: the damage is p_rpg's
+  int32_t game_words, tile_word;     // a game's LDS and its tile's offset in it, in uint32 (x 4)
+  uint32_t inv_ww, inv_v;            // recip(WW) (WW > 1), recip(V)
+};
+
+// A WAVE IS A GAME, as in route_kernel, and the search is one Dijkstra
+// backwards from the staircases, a bit-parallel step per tick of game time.
+// Three planes of H * WW words in LDS: `open` (Ground not yet given a value)
+// and the emitting set, double-buffered.  E(t), the emitting set of step t, is
+// every cell c with enter(c) + T(c) == t: a free cell given its value at t - 1,
+// a held cell hits(c) steps later (its RELEASE), a staircase from T = 0.  The
+// cells beside E(t) that are still open get T = t and leave `open`; those no
+// NPC holds are E(t + 1).  Values are given in nondecreasing order and a cell
+// keeps the first, so this is Dijkstra.  Lane k % 64 owns NPC slot k (in
+// kPasses passes, one while K <= 64): it sees its cell leave `open`, takes it out of the next
+// emitting set and notes the step of its release, at which it puts it back --
+// both lane by lane, so no two lanes change one word at once (no atomics).
+// When a step gives no value, the wave jumps to the least pending release.
+// The move needs no second search and no values kept: the own cell gets its
+// value at the step t where a neighbour is in E(t), and the neighbours in
+// E(t) are exactly those with enter + T == ticks.  Without a window the
+// search ends there; with one it runs out, and every step writes t for the
+// cells of the window it gives a value, into a V x V uint16 tile in LDS that
+// the wave streams out at the end.  Steps only visit the rows that hold a
+// valued cell, and one more each way.  Synchronisation is wave-local
+// throughout (wave_sync), no workgroup barrier: searches differ in length.
+template <int kPasses>
+__global__ __launch_bounds__(kBlock) void ticks_kernel(const TicksArgs a) {
+  extern __shared__ uint4 smem[];
+  const int W = a.W, H = a.H, WW = a.WW, words = H * WW, K = a.K;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t B = a.B, b = (int64_t)blockIdx.x * a.G + wave;
+  if (b >= B) return;  // (no workgroup barrier below: a wave is on its own)
+  uint32_t* const lds = reinterpret_cast<uint32_t*>(smem) + (size_t)wave * (size_t)a.game_words;
+  uint32_t* const open = lds;
+  uint32_t* cur = lds + words;
+  uint32_t* nxt = lds + 2 * words;
+  uint16_t* const tile = reinterpret_cast<uint16_t*>(lds + a.tile_word);  // (16-byte aligned)
+
+  const int64_t me = player_rows(a.player, B, b).me;
+  const int px = a.p_x[me], py = a.p_y[me];
+  const int R = a.R, V = 2 * R + 1, VV = V * V;
+  const bool windowed = a.window != nullptr;
+  const bool inside = (uint32_t)px < (uint32_t)W && (uint32_t)py < (uint32_t)H;
+  // a window that holds a cell of the grid (else it is Wall throughout)
+  const bool near = windowed && px >= -R && px < W + R && py >= -R && py < H + R;
+  const int oi = inside ? py * WW + (px >> 5) : 0;
+  const uint32_t obit = inside ? 1u << (px & 31) : 0u;
+
+  // row of word i (< 2^16)
+  auto row_of = [&](int i) { return WW == 1 ? i : (int)__umulhi((uint32_t)i, a.inv_ww); };
+
+  int32_t ticks = -1;
+  uint32_t mv = ORX_MOVE_STAY;
+  if (inside || near) {
+    // the planes: open = Ground, cur = the staircases; the rows that hold one
+    const int last_word = (W - 1) >> 5;
+    const uint32_t last_bit = 1u << ((W - 1) & 31);
+    const uint32_t* ground = nullptr;
+    int sx = -1, sy = -1;
+    if (a.L > 0) ground = a.planes + (size_t)layout_of(a, me) * 2u * (size_t)words;
+    else sx = a.st_x[me], sy = a.st_y[me];
+    uint32_t first = (uint32_t)H, last_inv = ~0u;  // (the last row as its complement: a minimum)
+    for (int i = lane; i < words; i += 64) {
+      const int yy = row_of(i), xw = i - yy * WW;
+      RoomWord w;
+      if (ground) {
+        w.ground = ground[i], w.stair = ground[words + i];
+      } else {
+        const uint32_t in = xw == last_word ? (last_bit << 1) - 1u : ~0u;
+        w = room_word(W, H, sx, sy, yy, xw, last_word, last_bit, in);
+      }
+      open[i] = w.ground, cur[i] = w.stair, nxt[i] = 0u;
+      if (w.stair) {
+        first = (uint32_t)yy < first ? (uint32_t)yy : first;
+        last_inv = ~(uint32_t)yy < last_inv ? ~(uint32_t)yy : last_inv;
+      }
+    }
+    int lo = (int)wave_min(first), hi = (int)~wave_min(last_inv);
+    wave_sync();
+
+    // the window's tile as the tiles alone say it; the search fills in the rest
+    if (windowed) {
+      for (int c = lane; c < VV; c += 64) {
+        const int j = (int)__umulhi((uint32_t)c, a.inv_v), x = px + (c - j * V) - R, y = py + j - R;
+        uint32_t val = kWall;
+        if (near && (uint32_t)x < (uint32_t)W && (uint32_t)y < (uint32_t)H) {
+          const int wi = y * WW + (x >> 5);
+          val = (cur[wi] >> (x & 31)) & 1u ? 0u : (open[wi] >> (x & 31)) & 1u ? kFar : kWall;
+        }
+        tile[c] = (uint16_t)val;
+      }
+    }
+    const bool own_ground = inside && (open[oi] & obit), own_stair = inside && (cur[oi] & obit);
+    if (own_stair) ticks = 0;
+
+    // the NPC slots: a = max(damage - armor, 0) (past 127 every NPC falls at a blow)
+    int64_t att = (int64_t)(a.character
+                                ? a.p_rpg[(int64_t)(ORX_RPG_DAMAGE * 2 + a.player) * B + b]
+                                : a.damage) - (int64_t)a.armor;
+    att = att < 0 ? 0 : att > 127 ? 127 : att;
+    uint32_t s_cell[kPasses], s_hits[kPasses], s_rel[kPasses];
+    uint32_t on_stair = 0;  // bit p: pass p's slot stands on a staircase
+    bool mine = false;
+    const bool npcs_here = K > 0 && a.p_depth[me] == a.npc_depth;
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) {
+      const int k = p * 64 + lane;
+      s_cell[p] = 0u, s_hits[p] = 0u, s_rel[p] = kNever;
+      if (!npcs_here || k >= K) continue;
+      if (!((a.npc_alive[(int64_t)(k >> 5) * B + b] >> (k & 31)) & 1u)) continue;
+      const uint32_t pos = a.npc_pos[(int64_t)k * B + b];
+      const int x = (int)(pos & 0xFFu), y = (int)(pos >> 8);
+      if (x >= W || y >= H) continue;
+      const int wi = y * WW + (x >> 5);
+      int h = a.npc_health[(int64_t)k * B + b];
+      h = h < 1 ? 1 : h;
+      s_cell[p] = (uint32_t)wi << 5 | (uint32_t)(x & 31);
+      s_hits[p] = att > 0 ? (uint32_t)((h + (int)att - 1) / (int)att) : 0u;
+      if ((open[wi] >> (x & 31)) & 1u) {
+        s_rel[p] = kWaiting, mine = true;
+      } else if ((cur[wi] >> (x & 31)) & 1u) {  // on a staircase: T = 0, held from the start
+        s_rel[p] = att > 0 ? s_hits[p] + 1u : kNever, on_stair |= 1u << p, mine = true;
+      }
+    }
+    const bool any_npc = __ballot(mine) != 0ull;
+    wave_sync();  // (the tile and the slots have read the staircases)
+    lane_by_lane(on_stair != 0u, lane, [&]() {
+#pragma unroll
+      for (int p = 0; p < kPasses; ++p)
+        if ((on_stair >> p) & 1u) cur[s_cell[p] >> 5] &= ~(1u << (s_cell[p] & 31));
+    });
+
+    // The loop cannot stall.  A pass either gives a value to at least one open
+    // cell -- at most W * H passes do -- or gives none; then it ends the
+    // search, or jumps to the least pending release, which is then due at the
+    // top of the next pass and is spent there -- at most K passes do.  t only
+    // grows, by one or to a release later than t, and never passes a release:
+    // one noted at step t is due at t + 2 or later.  So W * H + K + 1 passes
+    // suffice; the bound below is the largest value, which is no less.
+    const bool wanted = own_ground || near;
+    const uint32_t bound = (uint32_t)(W * H + 128 * K + 1);
+    uint32_t t = 1;
+    for (uint32_t pass = 0; wanted && lo <= hi && pass < bound; ++pass) {
+      // the releases due now join the emitting set
+      if (any_npc) {
+        bool due = false;
+#pragma unroll
+        for (int p = 0; p < kPasses; ++p) due |= s_rel[p] == t;
+        lane_by_lane(due, lane, [&]() {
+#pragma unroll
+          for (int p = 0; p < kPasses; ++p)
+            if (s_rel[p] == t) cur[s_cell[p] >> 5] |= 1u << (s_cell[p] & 31), s_rel[p] = kNever;
+        });
+      }
+
+      // the step: the open cells beside the emitting set get T = t
+      lo = lo > 0 ? lo - 1 : 0, hi = hi < H - 1 ? hi + 1 : H - 1;
+      uint32_t grew = 0;
+      for (int i = lo * WW + lane; i < (hi + 1) * WW; i += 64) {
+        const int yy = row_of(i), xw = i - yy * WW;
+        const uint32_t o = open[i];
+        const uint32_t fresh = beside(cur, cur[i], i, yy, xw, WW, H) & o;
+        nxt[i] = fresh;
+        if (!fresh) continue;
+        open[i] = o & ~fresh;
+        grew |= fresh;
+        const int j = yy - py + R;  // the window's row
+        if (near && (uint32_t)j < (uint32_t)V) {
+          const int x0 = px - R - xw * 32;  // the window's first column, as a bit of this word
+          const int from = x0 > 0 ? x0 : 0, to = x0 + V - 1 < 31 ? x0 + V - 1 : 31;
+          if (from <= to) {
+            uint32_t m = fresh & ((2u << to) - 1u) & ~((1u << from) - 1u);
+            for (; m; m &= m - 1) tile[j * V + __builtin_ctz(m) - x0] = (uint16_t)t;
+          }
+        }
+      }
+      wave_sync();
+
+      // a held cell that got its value waits for its release
+      if (any_npc) {
+        bool met = false;
+#pragma unroll
+        for (int p = 0; p < kPasses; ++p) {
+          if (s_rel[p] != kWaiting || ((open[s_cell[p] >> 5] >> (s_cell[p] & 31)) & 1u)) continue;
+          s_rel[p] = t;  // (met now: marked by the step, replaced below)
+          met = true;
+        }
+        lane_by_lane(met, lane, [&]() {
+#pragma unroll
+          for (int p = 0; p < kPasses; ++p)
+            if (s_rel[p] == t) nxt[s_cell[p] >> 5] &= ~(1u << (s_cell[p] & 31));
+        });
+#pragma unroll
+        for (int p = 0; p < kPasses; ++p)
+          if (s_rel[p] == t) s_rel[p] = att > 0 ? t + s_hits[p] + 1u : kNever;
+      }
+
+      // the own cell: its value, and the first neighbour that emitted it
+      if (own_ground && ticks < 0 && !(open[oi] & obit)) {
+        ticks = (int32_t)t;
+        bool step = false;
+        if (lane < 4) {
+          const int nx = px + (lane == 1) - (lane == 3), ny = py + (lane == 2) - (lane == 0);
+          if ((uint32_t)nx < (uint32_t)W && (uint32_t)ny < (uint32_t)H)
+            step = (cur[ny * WW + (nx >> 5)] >> (nx & 31)) & 1u;
+        }
+        const uint32_t nib = (uint32_t)__ballot(step) & 15u;
+        mv = nib ? (uint32_t)(ORX_MOVE_UP + __builtin_ctz(nib)) : (uint32_t)ORX_MOVE_STAY;
+        if (!near) break;
+      }
+
+      uint32_t* const swap = cur;
+      cur = nxt, nxt = swap;
+      if (__ballot(grew != 0u) != 0ull) {
+        ++t;
+        continue;
+      }
+      uint32_t pending = kNever;  // (a release noted is later than t)
+#pragma unroll
+      for (int p = 0; p < kPasses; ++p) pending = s_rel[p] < pending ? s_rel[p] : pending;
+      pending = any_npc ? wave_min(pending) : kNever;
+      if (pending >= kNever) break;
+      t = pending;
+    }
+    wave_sync();
+  } else if (windowed) {
+    for (int c = lane; c < VV; c += 64) tile[c] = (uint16_t)kWall;
+    wave_sync();
+  }
+
+  if (windowed) stream_out<uint16_t, 64>(tile, a.window + (size_t)b * (size_t)VV, VV, lane);
+  if (lane != 0) return;
+  if (a.ticks) a.ticks[b] = ticks;
+  if (a.move) a.move[b] = (int8_t)mv;
+}
+
 }  // namespace orx_path_dev
 
 #ifndef ORX_PATH_BUILD_ID
@@ -1068,4 +1332,81 @@ extern "C" int orx_path_threat(const orx_cfg_t* cfg, const orx_state_t* st, cons
   const unsigned grid = (unsigned)((n_games + G - 1) / G);
   hipLaunchKernelGGL(threat_window_kernel, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, a);
   return orx_dev::launch_status("orx_path_threat");
+}
+
+extern "C" int orx_path_ticks(const orx_cfg_t* cfg, const orx_state_t* st, const uint32_t* planes,
+                              int32_t player, int32_t radius, int32_t* ticks, int8_t* move,
+                              uint16_t* window, int64_t n_games, void* stream) {
+  using namespace orx_path_dev;
+  using orx_dev::fail;
+  int r;
+  if ((r = orx_validate_cfg(cfg)) || (r = check_player("orx_path_ticks", player))) return r;
+  if (!ticks && !move && !window)
+    return fail(ORX_EINVAL, "orx_path_ticks: ticks, move and window are all NULL");
+  if (window && (radius < 1 || radius > ORX_VIEW_MAX_RADIUS))
+    return fail(ORX_EINVAL, "orx_path_ticks: radius must be in [1, ORX_VIEW_MAX_RADIUS]");
+  if (misaligned(ticks, 4) || misaligned(window, 2) || misaligned(planes, 4))
+    return fail(ORX_EINVAL,
+                "orx_path_ticks: ticks and planes must be 4-byte and window 2-byte aligned");
+  if ((r = check_games("orx_path_ticks", n_games))) return r;
+  if ((int64_t)cfg->width * cfg->height > 65536)
+    return fail(ORX_EINVAL, "orx_path_ticks: a plane's words must fit 16 bits (W * H <= 65536)");
+  if ((r = check_state(cfg, st, kStairsNoBank | kBank | kNpcs | kCharacter))) return r;
+  if (!st->p_depth) return fail(ORX_EINVAL, "a required state pointer is NULL");
+  if (cfg->n_layouts > 0 && !planes)
+    return fail(ORX_EINVAL, "orx_path_ticks: n_layouts > 0 needs planes");
+  // the largest value, every cell entered once and every NPC at 127 hits, must
+  // stay below the sentinels
+  if (window && (int64_t)cfg->width * cfg->height + 127 * (int64_t)cfg->n_npcs >=
+                    (int64_t)ORX_PATH_UNREACHABLE)
+    return fail(ORX_EINVAL, "orx_path_ticks: W * H + 127 * n_npcs too large for a window of "
+                            "uint16 values");
+  if (cfg->n_npcs > 64 * kSlotPasses) return fail(ORX_EINVAL, "orx_path_ticks: too many NPCs");
+
+  TicksArgs a;
+  a.p_x = st->p_x, a.p_y = st->p_y, a.p_depth = st->p_depth;
+  a.st_x = st->st_x, a.st_y = st->st_y, a.p_rpg = st->p_rpg;
+  a.p_layout = st->p_layout;
+  a.npc_pos = st->npc_pos, a.npc_health = st->npc_health, a.npc_alive = st->npc_alive;
+  a.planes = cfg->n_layouts > 0 ? planes : nullptr;
+  a.ticks = ticks, a.move = move, a.window = window;
+  a.B = n_games;
+  a.W = cfg->width, a.H = cfg->height, a.WW = (cfg->width + 31) / 32, a.L = cfg->n_layouts;
+  a.K = cfg->n_npcs, a.player = player, a.npc_depth = npc_depth(cfg);
+  a.R = window ? radius : 0;
+  a.damage = cfg->player_damage, a.armor = cfg->player_armor;
+  a.character = (cfg->flags & ORX_EXT_CHARACTER) ? 1 : 0;
+  a.inv_ww = recip(a.WW > 1 ? a.WW : 2);
+  a.inv_v = recip(2 * a.R + 1);
+  // a wave per game: three planes and the window's tile, each a whole number of uint4
+  const int V = 2 * a.R + 1;
+  a.tile_word = (kTicksPlanes * a.H * a.WW + 3) & ~3;
+  a.game_words = a.tile_word + (window ? ((V * V + 1) / 2 + 3) & ~3 : 0);
+  const size_t game_bytes = sizeof(uint32_t) * (size_t)a.game_words;
+  const int G = a.G = games_per_workgroup(game_bytes);
+  const size_t lds = (size_t)G * game_bytes;
+  // (narrow and tall, W <= 64 and H in the thousands: three planes pass the CU's 160 KiB)
+  if (lds > 160 * 1024)
+    return fail(ORX_EIO, "orx_path_ticks: a game's planes need more LDS than the device has");
+  if (lds > (size_t)kDefaultLds) {
+    // (above the default limit of dynamic LDS: asked for once)
+    static const hipError_t raised =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(ticks_kernel<1>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess
+            ? hipErrorInvalidValue
+            : hipFuncSetAttribute(reinterpret_cast<const void*>(ticks_kernel<kSlotPasses>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (raised != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ORX_EIO, "orx_path_ticks: the device refuses the LDS a game's planes need");
+    }
+  }
+  const unsigned grid = (unsigned)((n_games + G - 1) / G);
+  // (a lane owns one slot while K <= 64: the form without the passes' loops)
+  if (a.K <= 64)
+    hipLaunchKernelGGL(ticks_kernel<1>, dim3(grid), dim3(64 * G), lds, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(ticks_kernel<kSlotPasses>, dim3(grid), dim3(64 * G), lds,
+                       (hipStream_t)stream, a);
+  return orx_dev::launch_status("orx_path_ticks");
 }

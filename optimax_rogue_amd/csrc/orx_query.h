@@ -90,16 +90,18 @@ __device__ __forceinline__ uint32_t spread4(uint32_t n) {
 }
 
 // tile[0 .. n) (LDS, 16-byte aligned) -> out[0 .. n): 16 bytes per lane while
-// out is 16-byte aligned, the rest (all of it, if out is not) element by element
-template <typename T>
+// out is 16-byte aligned, the rest (all of it, if out is not) element by element.
+// t: the thread's index among the kThreads that stream (a workgroup; a wave
+// that owns its tile: 64).
+template <typename T, int kThreads = kBlock>
 __device__ __forceinline__ void stream_out(const T* tile, T* out, int n, int t) {
   static_assert(sizeof(T) == 1 || sizeof(T) == 2, "1 or 2-byte cells");
   constexpr int kShift = sizeof(T) == 1 ? 4 : 3;  // log2 of the elements per uint4
   const int nvec = ((reinterpret_cast<uintptr_t>(out) & 15) == 0) ? n >> kShift : 0;
   const uint4* src = reinterpret_cast<const uint4*>(tile);
   uint4* dst = reinterpret_cast<uint4*>(out);
-  for (int v = t; v < nvec; v += kBlock) dst[v] = src[v];
-  for (int i = (nvec << kShift) + t; i < n; i += kBlock) out[i] = tile[i];
+  for (int v = t; v < nvec; v += kThreads) dst[v] = src[v];
+  for (int i = (nvec << kShift) + t; i < n; i += kThreads) out[i] = tile[i];
 }
 
 // a layout index clamped into a bank of L > 0 layouts (the lookup must stay

@@ -38,7 +38,9 @@
 // wait for each other.  Every loop is bounded by the step count (<= W * H) and
 // ends at a step that reaches nothing new.  The key's rule, the wave's
 // reductions, the dist / move stores and the host side's refusals are
-// orx_seek.h's, shared with orx_explore.hip; frontier_bits is there too.  Plain C++ and vector stores only;
+// orx_seek.h's, shared with orx_explore.hip; frontier_bits is there too, and so
+// are the step itself (beside) and the room's words (room_word), which
+// orx_path_ticks shares.  Plain C++ and vector stores only;
 // no atomics; each output row is one store from lane 0.
 #include "../../include/orx_route.h"
 #include "orx_query.h"
@@ -108,13 +110,10 @@ struct Map {
     uint32_t g = 0, s = 0;
     if (ground) {
       g = ground[i], s = stair[i];
-    } else if (y > 0 && y < H - 1) {
+    } else {
       // EmptyDungeonGenerator: the border Wall, one staircase off the border
-      g = in;
-      if (xw == 0) g &= ~1u;
-      if (xw == last_word) g &= ~last_bit;
-      if (y == sy && sx >= 1 && sx <= W - 2 && (sx >> 5) == xw) s = 1u << (sx & 31);
-      g &= ~s;
+      const RoomWord room = room_word(W, H, sx, sy, y, xw, last_word, last_bit, in);
+      g = room.ground, s = room.stair;
     }
     r.pass = k & g, r.stairs = k & s;
     if (want_front && r.pass)
@@ -227,11 +226,7 @@ __global__ __launch_bounds__(kBlock) void route_kernel(const RouteArgs a) {
       for (int i = lo * WW + lane; i < (hi + 1) * WW; i += 64) {
         const int yy = row_of(i), xw = i - yy * WW;
         const uint32_t c = cur[i];
-        uint32_t nb = c << 1 | c >> 1;
-        if (xw > 0) nb |= cur[i - 1] >> 31;
-        if (xw < WW - 1) nb |= cur[i + 1] << 31;
-        if (yy > 0) nb |= cur[i - WW];
-        if (yy < H - 1) nb |= cur[i + WW];
+        const uint32_t nb = beside(cur, c, i, yy, xw, WW, H);
         const Word w = word_at(i, yy, xw, hits && (pending & 1u));
         const uint32_t fresh = nb & ~c & w.pass;
         nxt[i] = c | fresh;

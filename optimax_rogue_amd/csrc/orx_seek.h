@@ -93,6 +93,39 @@ __device__ __forceinline__ uint32_t frontier_bits(const uint32_t* known, uint32_
   return k & ~(up & down & left & right);
 }
 
+// One step of a bit-parallel search over a plane of H rows of WW words: the
+// cells beside those of `cur`, for word i (row y, word xw of the row; c =
+// cur[i]) -- the word shifted left and right with the carry bits of the words
+// beside it, ORed with the words above and below.  orx_route's search and
+// orx_path_ticks' both take their steps with it.
+__device__ __forceinline__ uint32_t beside(const uint32_t* cur, uint32_t c, int i, int y, int xw,
+                                           int WW, int H) {
+  uint32_t nb = c << 1 | c >> 1;
+  if (xw > 0) nb |= cur[i - 1] >> 31;
+  if (xw < WW - 1) nb |= cur[i + 1] << 31;
+  if (y > 0) nb |= cur[i - WW];
+  if (y < H - 1) nb |= cur[i + WW];
+  return nb;
+}
+
+// Word xw of row y of EmptyDungeonGenerator's W x H room as bit planes: the
+// border Wall, the rest Ground but for the one staircase (sx, sy) off the
+// border.  `in`: the word's columns x < W; last_word, last_bit: the word and
+// the bit of column W - 1.
+struct RoomWord { uint32_t ground, stair; };
+__device__ __forceinline__ RoomWord room_word(int W, int H, int sx, int sy, int y, int xw,
+                                              int last_word, uint32_t last_bit, uint32_t in) {
+  RoomWord r = {0u, 0u};
+  if (y > 0 && y < H - 1) {
+    r.ground = in;
+    if (xw == 0) r.ground &= ~1u;
+    if (xw == last_word) r.ground &= ~last_bit;
+    if (y == sy && sx >= 1 && sx <= W - 2 && (sx >> 5) == xw) r.stair = 1u << (sx & 31);
+    r.ground &= ~r.stair;
+  }
+  return r;
+}
+
 // the least of a word over the wave
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 #pragma unroll
@@ -108,6 +141,16 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// fn() by the lanes that say `mine`, one after the other, each seeing the LDS
+// stores of those before it: how lanes change bits of one word without atomics
+template <typename Fn>
+__device__ __forceinline__ void lane_by_lane(bool mine, int lane, Fn fn) {
+  for (uint64_t m = __ballot(mine); m; m &= m - 1) {
+    if (lane == __builtin_ctzll(m)) fn();
+    wave_sync();
+  }
 }
 
 // Row `row` of a seek's dist ([.][ORX_SEEK_COLS] int32) and move

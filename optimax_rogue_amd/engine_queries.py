@@ -363,6 +363,62 @@ class EngineQueries:
                    self._stream())
         return tuple(outs)
 
+    def path_ticks(self, player: int = 0, radius: Optional[int] = None, out=None):
+        """orx_path_ticks (include/orx_path.h): in how many ticks ``player`` (0
+        / 1) of every game can descend, with the live NPCs of its depth in the
+        way -- ``path`` where a step onto an NPC's cell is the attack it is:
+        entering a held cell costs a tick per blow (``ceil(health / (damage -
+        armor))``) and one for the step, and the cheaper of fighting through
+        and walking round is taken.  Returns ``(ticks, move)``: int32
+        [n_games], -1 where no staircase can be reached, and int8 [n_games],
+        the first of Up, Right, Down, Left that is on a fastest way (an attack
+        where that way goes through an NPC; Stay on a staircase or where none
+        can be reached; ready as ``actions``).  With a ``radius`` (1..15) also
+        ``window``, uint16 [n_games, V, V]: the ticks of every cell in
+        ``view``'s geometry and ``path``'s format.  Exact with flags 0 against
+        NPCs that stay and the other player out of the way: playing ``move``
+        lowers ``ticks`` by one per tick; an upper bound under EXT_MANA and
+        EXT_ITEMS, an estimate against moving NPCs.  Always ``ticks >= path's
+        dist``, equal where no NPC lives.  One launch on the current stream, a
+        search per game on the device, no host sync, no state change, no
+        random words; with a bank the first call also packs ``route_planes``.
+        ``out``: a ``(ticks, move)`` or ``(ticks, move, window)`` tuple of
+        tensors written and returned instead of fresh ones.  The host
+        reference is ``path.ticks(self.snapshot(), ...)``."""
+        from .query import check_player, check_radius
+        check_player(player)
+        if radius is not None:
+            check_radius(radius)
+        self._require("orx_path_ticks")
+        specs = [(torch.int32, (self.B,)), (torch.int8, (self.B,))]
+        if radius is not None:
+            V = 2 * int(radius) + 1
+            specs.append((torch.uint16, (self.B, V, V)))
+        outs = self._outs(out, specs, "(ticks, move), or (ticks, move, window) with a radius")
+        self._refuse_wide_cells("path_ticks")
+        if radius is not None and int(self.cfg.width) * int(self.cfg.height) \
+                + 127 * int(self.cfg.n_npcs) >= 0xFFFE:
+            raise ValueError("path_ticks: width * height + 127 * n_npcs too large for a window of "
+                             "uint16 values")
+        planes = self.route_planes
+        self._call("orx_path_ticks", _ptr(planes), int(player), int(radius or 0), _ptr(outs[0]),
+                   _ptr(outs[1]), _ptr(outs[2]) if radius is not None else None, self.B,
+                   self._stream())
+        return tuple(outs)
+
+    def rush_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games], ready as ``actions``: ``path_ticks``'s move alone
+        (orx_path_ticks with its other outputs NULL) -- the fastest way down,
+        through an NPC where the fight is quicker than the way round."""
+        from .query import check_player
+        check_player(player)
+        self._require("orx_path_ticks")
+        self._refuse_wide_cells("rush_moves")
+        move = torch.empty((self.B,), dtype=torch.int8, device=self.device)
+        self._call("orx_path_ticks", _ptr(self.route_planes), int(player), 0, None, _ptr(move), None,
+                   self.B, self._stream())
+        return move
+
     # the largest pair table ``pair_field`` builds: 2 * L * (W * H)^2 bytes
     PAIR_FIELD_MAX_BYTES = 1 << 30
 

@@ -31,12 +31,17 @@ staircase but not cross one: the interior cells of a path are all Ground.
 distances from what hunts a player -- the other player, the live NPCs -- to its
 own cell, to each move's cell and to every cell of a window, and the move after
 which it is largest (``flee_moves``).
+
+``ticks`` (``orx_path_ticks``) is ``query`` with the enemies in the way: a step
+onto a live NPC's cell is an attack that leaves the mover where it is
+(updater.py:218-227), so entering a held cell costs one tick per blow and one
+for the step -- a shortest path with small integer entry costs, per game.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .enums import Move, Tile
+from .enums import EXT_CHARACTER, RPG_FIELDS, Move, Tile
 from .query import (MOVE_DELTAS, bank_at, bank_of, check_player, check_radius, i64, inside_grid,
                     item_rows, npc_depth, npc_rows, per_game, tile_at, window_cells)
 
@@ -465,3 +470,114 @@ def flee_moves(move) -> np.ndarray:
     """int8 [B]: column THREAT_ANY of ``threat``'s ``move`` -- the step that
     puts the most walking distance between the player and what hunts it."""
     return np.asarray(move)[:, THREAT_ANY].astype(np.int8)
+
+
+# -- ticks to the staircase through the enemies (orx_path_ticks) ---------------
+def ticks(snap: dict, cfg, player: int, radius=None, bank=None):
+    """``(ticks, move)`` of ``player`` (0 / 1) of every game of a
+    ``snapshot()``-shaped dict, and with a ``radius`` ``(ticks, move, window)``:
+    ``query`` with the live NPCs of the player's depth in the way.
+
+    A live NPC (alive bit set, in the grid, the player on the NPCs' depth) holds
+    its cell: with ``a = max(damage - player_armor, 0)`` -- ``damage`` the
+    player's ``p_rpg`` row under a character flag, ``cfg.player_damage``
+    otherwise -- entering it costs ``1 + ceil(max(health, 1) / a)`` ticks, and
+    it cannot be entered when ``a == 0``; every other cell costs 1.  ``T`` of a
+    cell is the least total over a walk from it to a StaircaseDown (every cell
+    stepped onto, the staircase included; interior cells all Ground), 0 on a
+    staircase.
+
+    ticks   int32 [B]: ``T`` of the own cell; -1 where there is no walk, or the
+            own cell is a Wall or outside the grid
+    move    int8 [B]: the first of Up, Right, Down, Left whose neighbour's entry
+            cost plus ``T`` is ``ticks``; Stay when ``ticks <= 0``
+    window  uint16 [B, V, V]: ``T`` in ``query``'s format and geometry
+            (PATH_WALL, PATH_UNREACHABLE)
+
+    Exact with flags 0 against NPCs that stay: playing ``move`` lowers ``ticks``
+    by one per tick and descends where it was 1.  A Dijkstra over all games at
+    once, by steps of game time: the cells that emit at step t give t to their
+    open neighbours, which emit ``enter`` steps later."""
+    import heapq
+    check_player(player)
+    if radius is not None:
+        check_radius(radius)
+    bank = bank_of(cfg, bank)
+    p, K = int(player), int(cfg.n_npcs)
+    W, H = int(cfg.width), int(cfg.height)
+    px, py = i64(snap["p_x"][p]), i64(snap["p_y"][p])
+    B = len(px)
+    if radius is not None and W * H + 127 * K >= PATH_UNREACHABLE:
+        raise ValueError("width * height + 127 * n_npcs too large for a window of uint16 values")
+    X, Y = (np.broadcast_to(a, (B, W, H)) for a in np.indices((W, H)))
+    _, tile = tile_at(cfg, snap, p, X, Y, None if bank is None else bank.layouts)
+    # one Wall ring around every game's grid: a step off the grid lands on it
+    P = (W + 2) * (H + 2)
+    pad = np.full((B, W + 2, H + 2), int(Tile.Wall), np.int8)
+    pad[:, 1:-1, 1:-1] = tile
+    flat = pad.reshape(-1)
+    ground, stair = flat == int(Tile.Ground), flat == int(Tile.StaircaseDown)
+
+    # the held cells: hits per cell (the least over the slots on it), and
+    # whether it can be entered at all
+    damage = np.full(B, int(cfg.player_damage), np.int64)
+    if int(cfg.flags) & EXT_CHARACTER:
+        damage = i64(snap["p_rpg"][RPG_FIELDS.index("damage")][p])
+    a = np.maximum(damage - int(cfg.player_armor), 0)
+    never = np.int32(1) << 30
+    hits = np.full(B * P, never, np.int32)
+    if K > 0:
+        alive, nx, ny, hp = npc_rows(snap, K)
+        on = alive & (i64(snap["p_depth"][p]) == npc_depth(cfg))[None] & inside_grid(cfg, nx, ny)
+        blows = -(-np.maximum(hp, 1) // np.maximum(a, 1))                 # [K, B]
+        k, b = np.nonzero(on)
+        np.minimum.at(hits, b * P + (nx[k, b] + 1) * (H + 2) + ny[k, b] + 1, blows[k, b])
+    held = hits < never
+    barred = held & (np.repeat(a, P) == 0)
+    hits = np.where(held & ~barred, hits, 0)
+
+    T = np.full(B * P, -1, np.int32)
+    steps = np.array([-1, 1, -(H + 2), H + 2], np.int64)
+    due, order = {}, []                 # step -> the cells that emit then
+
+    def emit(cells, t):
+        cells = cells[~barred[cells]]
+        at = t + 1 + hits[cells].astype(np.int64)
+        for step in (np.unique(at) if held[cells].any() else at[:1]):
+            if int(step) not in due:
+                due[int(step)] = []
+                heapq.heappush(order, int(step))
+            due[int(step)].append(cells[at == step])
+
+    seeds = np.flatnonzero(stair)
+    T[seeds] = 0
+    emit(seeds, 0)
+    while order:
+        t = heapq.heappop(order)
+        nxt = (np.concatenate(due.pop(t))[:, None] + steps[None, :]).reshape(-1)
+        nxt = np.unique(nxt[ground[nxt] & (T[nxt] < 0)])
+        T[nxt] = t
+        emit(nxt, t)
+
+    T, hits, barred = (v.reshape(B, W + 2, H + 2) for v in (T, hits, barred))
+
+    def read(plane, x, y):
+        return plane[per_game(np.arange(B), x), np.clip(x, -1, W) + 1, np.clip(y, -1, H) + 1]
+
+    own = read(T, px, py)
+    out = np.where(inside_grid(cfg, px, py), own, -1).astype(np.int64)
+    move = np.full(B, int(Move.Stay), np.int8)
+    for code, dx, dy in reversed(MOVE_DELTAS):
+        x, y = px + dx, py + dy
+        via = inside_grid(cfg, x, y) & (read(T, x, y) >= 0) & ~read(barred, x, y)
+        cost = 1 + read(hits, x, y).astype(np.int64) + read(T, x, y)
+        move = np.where(via & (out > 0) & (cost == out), code, move)
+    out = out.astype(np.int32)
+    if radius is None:
+        return out, move.astype(np.int8)
+    wx, wy = window_cells(px, py, int(radius))
+    cell = inside_grid(cfg, wx, wy) & np.isin(read(pad, wx, wy), (int(Tile.Ground), int(Tile.StaircaseDown)))
+    value = read(T, wx, wy).astype(np.int64)
+    window = np.where(cell, np.where(value < 0, PATH_UNREACHABLE, value), PATH_WALL)
+    return out, move.astype(np.int8), window.astype(np.uint16)
+

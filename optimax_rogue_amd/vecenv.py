@@ -185,6 +185,24 @@ class VecEnv:
         the first wall in its way."""
         return self.engine.path(player=player)[1]
 
+    def path_ticks(self, player: int = 0, radius: Optional[int] = None, out=None):
+        """``(ticks, move)`` of ``player`` (0: the learner) of every game, and
+        with a ``radius`` also the uint16 ``window``: ``path`` with the live
+        NPCs in the way -- in how many ticks the player can descend when a
+        step onto an NPC's cell costs the blows it takes to kill it, and the
+        move on a fastest way, an attack where fighting through beats walking
+        round (``BatchedEngine.path_ticks``; one launch, a search per game, no
+        host sync).  ``ticks`` is the honest shaping potential where ``dist``
+        calls an NPC on the way free: exact against NPCs that stay, with the
+        other player out of the way."""
+        return self.engine.path_ticks(player=player, radius=radius, out=out)
+
+    def rush_moves(self, player: int = 0) -> torch.Tensor:
+        """int8 [n_games]: ``path_ticks``'s move -- ``stair_moves`` that knows
+        the enemies: it fights through an NPC where that is quicker than the
+        way round, and walks round where it is not (ready as ``actions``)."""
+        return self.engine.rush_moves(player=player)
+
     def seek(self, player: int = 0, out=None):
         """``(dist, move, target)`` of ``player`` (0: the learner) of every
         game, [n_games, 4] each: how many moves away the other player, the
